@@ -9,8 +9,10 @@ One "step" = the body of the reference's training loop (train.py:137-156) on one
 zero_grad, forward (forward_dec + forward_seg on the GT boxes), 4x DetectionLossAll + SEG_loss, backward,
 Adam step, loss.item().  Per GPU: batch 8 of 3x512x512 images with 300 GT boxes each (BASELINE configs[1]/[3],
 weak scaling).  Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line with the
-whole-job imgs/s, the roofline of the dominant kernel (HIP events around its launches during the timed steps) and a
-CPU baseline (the oracle's torch restatement of the same step, timed on the host cores, bounded sample).
+whole-job imgs/s.  A plain run does only that: set-up, warm-up, the timed steps, the line.  --full adds the roofline of the
+dominant kernel (HIP events around its launches during the timed steps), the other loss read-back / GC policies, the per-kernel
+pass, the `fp32b2` / `half` companions, a CPU baseline (the oracle's torch restatement of the same step, timed on the host cores,
+bounded sample) and the long-form details file.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import gc
@@ -503,6 +505,44 @@ ROOFLINE_NOTE = ("achieved = 16-bit MFMA FLOPs ISSUED by the launches of this ke
                  "tools/profile_round.sh on another box run")
 
 
+DUMP_MAX_ELEMS = 1_000_000     # per array: 15 float32 arrays stay under 64 MB in all
+
+
+def _sample(name, t):
+    """float32 numpy copy of `t` flattened in logical (NCHW) order; above DUMP_MAX_ELEMS a fixed sample of sorted indices seeded by
+    the array's name and size, so that two builds given the same arguments pick the same elements."""
+    import zlib
+    flat = t.detach().reshape(-1).float()
+    n = flat.numel()
+    if n > DUMP_MAX_ELEMS:
+        rng = np.random.default_rng([zlib.crc32(name.encode()), n])
+        idx = np.sort(rng.choice(n, DUMP_MAX_ELEMS, replace=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.cpu().numpy()
+
+
+def collect_outputs(model, kept, loss):
+    """What the caller of one train step receives, from the step's kept results: the loss, the 12 head maps (dec<level>_kp / _short /
+    _mid), the mask patches of the seg branch (seg_masks: image by image, boxes in input order, concatenated), and the model's
+    parameters after the Adam update and their gradients (params / grads: named_parameters order, a missing gradient as zeros)."""
+    out = {"loss": np.array([loss], np.float64)}
+    for lvl, maps in enumerate(kept["dec"]):
+        for hname, t in zip(("kp", "short", "mid"), maps):
+            out[f"dec{lvl}_{hname}"] = _sample(f"dec{lvl}_{hname}", t)
+    patches = [p.reshape(-1) for per_img in kept["pred"][0] for p in per_img]
+    out["seg_masks"] = _sample("seg_masks", torch.cat(patches)) if patches else np.zeros(0, np.float32)
+    params = [p for _, p in model.named_parameters()]
+    out["params"] = _sample("params", torch.cat([p.detach().reshape(-1).float() for p in params]))
+    out["grads"] = _sample("grads", torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1).float() for p in params]))
+    return out
+
+
+def write_outputs(path, outputs):
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -525,7 +565,15 @@ def main():
     ap.add_argument("--details", default=os.environ.get("KG_BENCH_DETAILS", ""),
                     help="file for the long-form record (per-kernel table, per-step times, companions with their roofline blocks, notes); default "
                          "gpurun_out/bench_details.json when that directory exists, else stderr.  The stdout JSON line stays under 3 KB")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: roofline of the dominant kernel, the other read-back / GC policies, the per-kernel pass, "
+                         "the companions, the CPU baseline, the details file (the --no-* switches and --profile-run thin it out again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, head maps, mask patches, updated parameters, "
+                         "gradients; arrays above 1e6 elements as a fixed seeded sample) as DIR/<name>.npy, float32 / float64")
     args = ap.parse_args()
+    if not args.full:
+        args.no_companion = args.no_cpu_baseline = args.no_kernel_timer = True
     if args.profile_run:
         args.no_companion = args.no_cpu_baseline = args.no_kernel_timer = True
 
@@ -559,9 +607,9 @@ def main():
         timer.install()
     ldec, lseg = DetectionLossAll(kp_radius=5), SEG_loss(height=args.size, width=args.size)
 
-    def run_train(precision, steps, warmup, sync_each_step, kernel_timer):
+    def run_train(precision, steps, warmup, sync_each_step, kernel_timer, keep_outputs=False):
         """K timed train steps of a fresh seeded model in `precision`; returns (seconds for the K steps = max over ranks, last loss,
-        per-step losses, dominant-kernel records)."""
+        per-step losses, dominant-kernel records, with keep_outputs the arrays of the last timed step: collect_outputs)."""
         torch.manual_seed(1234)
         model = KGnet.resnet50(pretrained=False, precision=precision).to(dev).train()
         parallel.broadcast_parameters(model)
@@ -570,9 +618,11 @@ def main():
         opt = Adam(filter(lambda p: p.requires_grad, model.parameters()), lr=1e-4, prepack=model)     # (prepack: packs the next forward's weights behind the update kernel)
         reducer = parallel.FlatGradReducer().attach(model) if world > 1 else None
 
-        def step(sync):
+        def step(sync, keep=None):
             opt.zero_grad()
             p0, p1, p2, p3, pred = model(x, gt_boxes)
+            if keep is not None:      # (last timed step of a --dump-outputs run: its results stay referenced until they are read back)
+                keep.update(dec=(p0, p1, p2, p3), pred=pred)
             if den is None:
                 l1 = ldec(p0, gt[0]) + ldec(p1, gt[1]) + ldec(p2, gt[2]) + ldec(p3, gt[3])
             else:
@@ -585,26 +635,26 @@ def main():
             opt.step()
             return loss.item() if sync else loss.detach()      # train.py:156 reads the loss back every step
 
-        def timed(K, sync, park_gc=True):
+        def timed(K, sync, park_gc=True, keep=None):
             if not park_gc:       # (what the drop-in train.py does: the cyclic collector stays on -- reported beside the headline)
-                return timed_(K, sync)
+                return timed_(K, sync, keep)
             # the K timed steps run with Python's cyclic collector parked (gc.freeze + disable, as training loops at scale do: a gen-2
             # pass over the model's ~10^5 objects is a multi-ms host stall at a random step); the step itself leaves no cycles behind
             # (tools/cycle_probe.py), so memory does not grow meanwhile
             gc.collect(); gc.freeze(); gc.disable()
             try:
-                return timed_(K, sync)
+                return timed_(K, sync, keep)
             finally:
                 gc.enable(); gc.unfreeze()
 
-        def timed_(K, sync):
+        def timed_(K, sync, keep=None):
             if world > 1:
                 dist.barrier()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             ls, mk = [], []
-            for _ in range(K):
-                ls.append(step(sync))
+            for i in range(K):
+                ls.append(step(sync, keep if i == K - 1 else None))
                 mk.append(time.perf_counter())
             torch.cuda.synchronize()
             if world > 1:
@@ -619,24 +669,30 @@ def main():
         for _ in range(warmup):
             step(sync_each_step)
         timer.on, timer.only_dominant, timer.rec = kernel_timer, True, []
-        dt_, ls, mk = timed(steps, sync_each_step)
+        kept = {} if keep_outputs else None
+        dt_, ls, mk = timed(steps, sync_each_step, keep=kept)
         timer.on = False
         res = {"dt": dt_, "losses": ls, "marks": mk, "dom_rec": timer.rec, "step": step, "timed": timed,
                "overflow": (lambda: model.grad_overflowed(reset=False))}
+        if keep_outputs:
+            res["outputs"] = collect_outputs(model, kept, ls[-1])
+            kept.clear()
         timer.rec = []
         return res
 
     # Headline: the K timed steps read the loss back EVERY step like train.py:156 (`running_loss += loss.item()`); KG_BENCH_SYNC=0
     # defers the read-back past the timed region instead (the host then enqueues step k+1 while the GPU still runs step k).
     STEP_SYNC = os.environ.get("KG_BENCH_SYNC", "1") == "1"
-    main_run = run_train(args.precision, args.steps, args.warmup, STEP_SYNC, not args.no_kernel_timer)
+    main_run = run_train(args.precision, args.steps, args.warmup, STEP_SYNC, not args.no_kernel_timer, keep_outputs=bool(args.dump_outputs) and rank == 0)
+    if "outputs" in main_run:
+        write_outputs(args.dump_outputs, main_run.pop("outputs"))
     dt, losses, marks = main_run["dt"], main_run["losses"], main_run["marks"][1:]
     t0 = main_run["marks"][0]
     last = losses[-1]
     dom_rec = main_run["dom_rec"]
     other_dt = dt
     gc_on_dt = None
-    if not args.profile_run:
+    if args.full and not args.profile_run:
         other_dt, _, _ = main_run["timed"](args.steps, not STEP_SYNC)      # the other loss-read-back policy, reported as a note
         gc_on_dt, _, _ = main_run["timed"](args.steps, STEP_SYNC, park_gc=False)   # the same steps with Python's cyclic GC left enabled
     overflowed = bool(main_run["overflow"]())
@@ -700,9 +756,13 @@ def main():
                       "precision_policy": args.precision, "planes": list(pol),
                       "global_batch": args.batch * world, "parallelism": f"dp{world}", "last_loss": last,
                       "loss_readback": "every step (train.py:156)" if STEP_SYNC else "after the timed region",
-                      "other_readback_policy_imgs_per_s": imgs / other_dt,
-                      "gc_enabled_imgs_per_s": (imgs / gc_on_dt) if gc_on_dt else None,
                       "grad_overflow": overflowed}}     # sticky device flag of the half-precision backward (KGnet.grad_overflowed): must be false
+    if not args.full:
+        print(json.dumps(out))
+        return
+    if not args.profile_run:
+        out["config"]["other_readback_policy_imgs_per_s"] = imgs / other_dt
+        out["config"]["gc_enabled_imgs_per_s"] = (imgs / gc_on_dt) if gc_on_dt else None
     # long-form record (side file, not the stdout line -- the driver keeps `config` scalars and cuts long strings / nested tables)
     details = {"precision": PDESC.get(args.precision, args.precision), "roofline_note": ROOFLINE_NOTE,
                "step_ms": [round(1e3 * (b - a), 2) for a, b in zip([t0] + marks[:-1], marks)]}

@@ -15,10 +15,10 @@ def pytest_configure(config):
 
 @pytest.fixture(scope="session")
 def golden():
-    import numpy as np
+    from oracle import fixtures
 
     def load(name):
-        return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
+        return fixtures.load(os.path.join(GOLDEN, name))
     return load
 
 

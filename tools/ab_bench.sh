@@ -8,7 +8,7 @@ BASE=${BASE:-libkgnet_hip_f16}
 for i in 1 2 3; do
   for L in ${BASE}_old.so ${BASE}.so; do
     echo -n "$L "
-    env $LIBVAR=$PWD/kg_instance_segmentation_amd/$L python bench.py --steps 10 --warmup 3 --no-companion --no-cpu-baseline "$@" 2>&1 | tail -1 |
+    env $LIBVAR=$PWD/kg_instance_segmentation_amd/$L python bench.py --full --steps 10 --warmup 3 --no-companion --no-cpu-baseline "$@" 2>&1 | tail -1 |
       python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], 'ms/step; dominant kernel', d['roofline']['achieved'], d['roofline']['unit'])"
   done
 done

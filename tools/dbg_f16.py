@@ -6,10 +6,10 @@ import numpy as np, torch
 from kg_instance_segmentation_amd import KGnet
 from kg_instance_segmentation_amd.loss import DetectionLossAll
 from kg_instance_segmentation_amd.seg_loss import SEG_loss
-from oracle import synth, weightgen
+from oracle import fixtures, synth, weightgen
 from tools.pareto import ratios, sub
 pol = sys.argv[1]
-g = np.load(os.path.join(ROOT, "tests", "golden", "net_cal.npz"), allow_pickle=False)
+g = fixtures.load(os.path.join(ROOT, "tests", "golden", "net_cal.npz"))
 sd = weightgen.gen_state_dict(0, variant="cal")
 m = KGnet.resnet50(pretrained=False, precision=pol); m.load_state_dict(sd); m = m.to("cuda").eval()
 m._engine.raw_kp_logits = True; m._seg.keep_logits = True

@@ -25,7 +25,7 @@ sys.path.insert(1, REF)
 import numpy as np
 import torch
 
-from oracle import net as onet, synth, weightgen
+from oracle import fixtures, net as onet, synth, weightgen
 
 cv2 = types.ModuleType("cv2")
 cv2.INTER_NEAREST = 0
@@ -138,7 +138,7 @@ def gen_postproc():
     assert len(np.unique(hb[:, 4])) == len(hb), "golden NMS input must not contain confidence ties"
     assert len(np.unique(g[:, 4])) == len(g)
     assert rnms.non_maximum_suppression_numpy(np.zeros((0, 5)), 0.5) is None
-    np.savez_compressed(os.path.join(GOLD, "postproc.npz"), **out)
+    fixtures.save(os.path.join(GOLD, "postproc.npz"), out)
     print("postproc.npz", {k: v.shape for k, v in out.items() if "skel" in k or "nms" in k})
 
 
@@ -216,7 +216,7 @@ def gen_net(seed=0):
     for k in ("bn1.running_mean", "bn1.running_var", "layer3.5.bn3.running_mean", "layer3.5.bn3.running_var",
               "layer2.0.downsample.1.running_var", "bn1.num_batches_tracked"):
         out[f"train.stat.{k}"] = msd[k].numpy()
-    np.savez_compressed(os.path.join(GOLD, "net.npz"), **out)
+    fixtures.save(os.path.join(GOLD, "net.npz"), out)
     print("net.npz written; losses", out["train.loss_dec"], out["train.loss_seg"], "patches", out["train.npatch"])
 
 
@@ -283,7 +283,7 @@ def gen_net_cal(seed=0):
     msd = model.state_dict()
     for k in ("bn1.running_mean", "bn1.running_var", "layer3.5.bn3.running_mean", "layer3.5.bn3.running_var"):
         out[f"train.stat.{k}"] = msd[k].numpy()
-    np.savez_compressed(os.path.join(GOLD, "net_cal.npz"), **out)
+    fixtures.save(os.path.join(GOLD, "net_cal.npz"), out)
     print("net_cal.npz written; losses", out["train.loss_dec"], out["train.loss_seg"], "patches", out["train.npatch"],
           "grad samples", out["train.grad_samples"].shape)
 
@@ -307,7 +307,7 @@ def gen_net_layers(seed=3, layers=(1, 2, 2, 1)):
                 out[f"c{l}.{nm}"] = sub(t)
         for l, f in enumerate(feats):
             out[f"feat{l}"] = sub(f, 5)[:, ::7].copy()
-    np.savez_compressed(os.path.join(GOLD, "net_layers.npz"), **out)
+    fixtures.save(os.path.join(GOLD, "net_layers.npz"), out)
     print("net_layers.npz written:", len(sd), "keys")
 
 
@@ -345,7 +345,7 @@ def gen_loss():
             out[f"seg.patch.{i}.{j}"] = p.numpy(); out[f"seg.det.{i}.{j}"] = dets[i][j].numpy()
         out[f"seg.gbox.{i}"] = gboxes[i]; out[f"seg.gmask.{i}"] = gmasks[i]
     assert rseg.SEG_loss(H2, W2)([[[patches[1][0]]], [[dets[1][0]]]], [gmasks[1]], [gboxes[1]]) is None
-    np.savez_compressed(os.path.join(GOLD, "loss.npz"), **out)
+    fixtures.save(os.path.join(GOLD, "loss.npz"), out)
     print("loss.npz", out["loss"], out["loss_empty"], out["seg.loss"])
 
 
@@ -384,7 +384,7 @@ def gen_preproc():
         out[f"{name}.bboxes"] = bb
         out[f"{name}.hw"] = np.array([H, W])
         out[f"{name}.gt"] = ref32
-    np.savez_compressed(os.path.join(GOLD, "preproc.npz"), **out)
+    fixtures.save(os.path.join(GOLD, "preproc.npz"), out)
     print("preproc.npz:", {k: v.shape for k, v in out.items() if k.endswith(".gt")})
 
 
@@ -448,7 +448,7 @@ def gen_evalparts():
     out["ap.rec"] = rec; out["ap.prec"] = prec
     out["ap.values"] = np.array([rev.voc_ap(rec, prec, True), rev.voc_ap(rec, prec, False)], np.float64)
     assert out["ap.values"][0] == oev.voc_ap(rec, prec, True) and out["ap.values"][1] == oev.voc_ap(rec, prec, False)
-    np.savez_compressed(os.path.join(GOLD, "evalparts.npz"), **out)
+    fixtures.save(os.path.join(GOLD, "evalparts.npz"), out)
     print("evalparts.npz:", len(out), "arrays; AP", out["ap.values"])
 
 

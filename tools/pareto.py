@@ -21,7 +21,7 @@ import torch
 from kg_instance_segmentation_amd import KGnet, engine
 from kg_instance_segmentation_amd.loss import DetectionLossAll
 from kg_instance_segmentation_amd.seg_loss import SEG_loss
-from oracle import synth, weightgen
+from oracle import fixtures, synth, weightgen
 
 DEV = "cuda"
 FP32 = (1e-4, 1e-5)      # rtol, atol (x max(1, rms))
@@ -116,7 +116,7 @@ def main():
     ap.add_argument("--no-bench", action="store_true")
     args = ap.parse_args()
     pols = args.policies or list(engine.PRECISIONS)
-    g = np.load(os.path.join(ROOT, "tests", "golden", "net_cal.npz"), allow_pickle=False)
+    g = fixtures.load(os.path.join(ROOT, "tests", "golden", "net_cal.npz"))
     sd = weightgen.gen_state_dict(0, variant="cal")
     table = {}
     for p in pols:
