@@ -247,6 +247,27 @@ int kg_skeleton_boxes(const double* skel, const int* nskel, int skel_cap, double
 int kg_nms(const double* boxes, const int* nbox, int box_cap, double thresh, void* ws, long ws_bytes, double* out,
            int* nkeep, void* stream);
 
+/* ---- batched post-processing: N images per launch (test.py:105-116 for a batch).  kg_postproc_scale, kg_skeleton_boxes and kg_nms are
+ * the N = 1 case of the same kernels; every result is bit-identical to the single-image call on that image's maps. ----
+ * workspace of kg_postproc_batch: N slices of kg_postproc_workspace_bytes(H, W, peak_cap, skel_cap) bytes (a multiple of 256), one per image
+ * (its own header, counters and fall-back flags); -1 on bad arguments */
+long kg_postproc_batch_workspace_bytes(int N, int H, int W, int peak_cap, int skel_cap);
+/* postprocessing.py:16-147 (Hough vote, Gaussian, peaks, grouping) of one scale for N images: kp [N][5][H][W], soff [N][10][H][W],
+ * mid [N][40][H][W] device fp32, contiguous.  Outputs: skel [N][skel_cap][5][3] f64, nskel [N] (skeletons found; may exceed skel_cap) */
+int kg_postproc_batch(const float* kp, const float* soff, const float* mid, int N, int H, int W, double thresh, void* ws,
+                      long ws_bytes, int peak_cap, int skel_cap, double* skel, int* nskel, void* stream);
+/* postprocessing.py:150-261 (refine + skeleton_to_box + gather_skeleton) for N images, one workgroup per image: skel, nskel, skel_cap and
+ * scale are HOST arrays of nscales (<= 4) entries, skel[s] = device [N][skel_cap[s]][5][3] f64, nskel[s] = device int [N]; the boxes of
+ * image n are appended scale after scale to boxes [N][box_cap][5] f64 from row 0, nbox[n] = their count (rows beyond box_cap dropped) */
+int kg_skeleton_boxes_batch(int N, int nscales, const double* const* skel, const int* const* nskel, const int* skel_cap,
+                            const double* scale, int do_refine, double* boxes, int* nbox, int box_cap, void* stream);
+/* workspace of kg_nms_batch: N slices of box_cap * 9 bytes (+ alignment); -1 on bad arguments */
+long kg_nms_batch_workspace_bytes(int N, int box_cap);
+/* nms.py:4-53 for N images, one workgroup per image over boxes [N][box_cap][5] / nbox [N]: nkeep[n] = boxes kept of image n, out = the kept
+ * rows of all images in pick order, image after image (image n from row nkeep[0] + .. + nkeep[n-1]); out holds N * box_cap rows */
+int kg_nms_batch(int N, const double* boxes, const int* nbox, int box_cap, double thresh, void* ws, long ws_bytes, double* out,
+                 int* nkeep, void* stream);
+
 /* ---- ground-truth maps of one pyramid scale (preprocessing.get_ground_truth, preprocessing.py:107-118, assembled and cast
  * as dataset_base.py:99-109): kps = device float32 [n][5][2] (x,y) keypoints tl,tr,bl,br,centre; out = device float32
  * [55][H][W] (kp 5 | short 10 | mid 40), bit-identical to the reference's float32 tensors ---- */

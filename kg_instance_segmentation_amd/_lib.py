@@ -75,6 +75,11 @@ _SIGS = {
     "kg_postproc_timing_end": [P],
     "kg_skeleton_boxes": [P, P, c_int, c_double, c_int, P, P, c_int, P],
     "kg_nms": [P, P, c_int, c_double, P, c_long, P, P, P],
+    "kg_postproc_batch_workspace_bytes": [c_int, c_int, c_int, c_int, c_int],
+    "kg_postproc_batch": [P, P, P, c_int, c_int, c_int, c_double, P, c_long, c_int, c_int, P, P, P],
+    "kg_skeleton_boxes_batch": [c_int, c_int, P, P, P, P, c_int, P, P, c_int, P],
+    "kg_nms_batch_workspace_bytes": [c_int, c_int],
+    "kg_nms_batch": [c_int, P, P, c_int, c_double, P, c_long, P, P, P],
     "kg_gt_maps": [P, c_int, c_int, c_int, P, P],
     "kg_adam_step": [P, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float, P],
     "kg_host_crop_masks": [P, P, c_int, c_int, c_int, P],
@@ -97,7 +102,7 @@ _SIGS = {
     "kg_mask_paste": [P, P, c_int, c_int, c_int, c_int, c_int, c_float, P, c_int, P],
     "kg_crop_grad_reduce": [P, c_int, P, c_int, c_long, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P],
 }
-_RESTYPE = {"kg_postproc_workspace_bytes": c_long}
+_RESTYPE = {"kg_postproc_workspace_bytes": c_long, "kg_postproc_batch_workspace_bytes": c_long, "kg_nms_batch_workspace_bytes": c_long}
 SYMBOLS = tuple(_SIGS) + ("kg_last_error", "kg_last_kernel")
 
 _lib = None

@@ -11,9 +11,18 @@
 //   P4 grouping     : greedy confidence-ordered star matching, one workgroup (4 waves = 4 edges)
 //   P6/P7 boxes     : refine + 8-case box assembly, ordered compaction, 4 scales appended
 //   P9 NMS          : greedy IoU suppression, one workgroup
+// Batched (kg_postproc_batch, kg_skeleton_boxes_batch, kg_nms_batch): P1-P4 take the image from blockIdx.z, P6/P7 and P9 from the
+// workgroup index; every image owns a workspace slice of a fixed byte stride (wsz), so its counters, flags and allocators are its own.
+// The single-image entry points are the N = 1 case of the same kernels.
 #include "kg_common.h"
 
 #define KG_NUM_KPS 5
+
+// slice of image blockIdx.z of a per-image buffer laid out at a stride of `bytes`
+template <class T>
+__device__ __forceinline__ T* zslice(T* p, long bytes) {
+    return reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(p) + (uintptr_t)((long)blockIdx.z * bytes));
+}
 
 __device__ __forceinline__ int f2i_np(double v) {  // numpy f64 -> int32 cast on x86 (cvttsd2si)
     if (!(v > -2147483649.0 && v < 2147483648.0)) return INT32_MIN;
@@ -67,8 +76,10 @@ __device__ __forceinline__ void hough_vote4(const float* __restrict__ kp, const 
 }
 
 // exclusive scan of count[c][0..HW) -> offs; one block (1024 threads) per channel.
-__global__ __launch_bounds__(1024) void scan_kernel(const int* __restrict__ count, int* __restrict__ offs, int n, int* __restrict__ total = nullptr) {
+__global__ __launch_bounds__(1024) void scan_kernel(const int* __restrict__ count, int* __restrict__ offs, int n, int* __restrict__ total,
+                                                    long wsz) {
     __shared__ int tot[1024];
+    count = zslice(count, wsz); offs = zslice(offs, wsz); total = zslice(total, wsz);
     const int* in = count + (long)blockIdx.x * n;
     int* out = offs + (long)blockIdx.x * n;
     const int per = (n + 1023) / 1024, b0 = threadIdx.x * per;
@@ -110,9 +121,12 @@ __device__ __forceinline__ bool hough_gave_up(const int* hdr) { return (hdr[1] |
 #define HOUGH_LCAP 512
 __global__ void hough_scatter_kernel(const float* __restrict__ kp, const float* __restrict__ soff, int H, int W, int* __restrict__ cnt,
                                      unsigned* __restrict__ ink, double* __restrict__ inv, int* __restrict__ ovcell,
-                                     double* __restrict__ ovval, const int* __restrict__ hdr) {
+                                     double* __restrict__ ovval, const int* __restrict__ hdr, long wsz) {
+    hdr = zslice(hdr, wsz);
     if (!hough_gave_up(hdr)) return;             // (the tile formulation produced the map)
     const int c = blockIdx.y, HW = H * W;
+    kp += (long)blockIdx.z * 5 * HW; soff += (long)blockIdx.z * 10 * HW;
+    cnt = zslice(cnt, wsz); ink = zslice(ink, wsz); inv = zslice(inv, wsz); ovcell = zslice(ovcell, wsz); ovval = zslice(ovval, wsz);
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < 4 * HW; e += gridDim.x * blockDim.x) {
         const int b = e / HW, i = e - b * HW;
         int cell; double v;
@@ -142,8 +156,11 @@ __global__ __launch_bounds__(1024) void hough_classify_kernel(int ncells, const 
                                                               const double* __restrict__ inv, double norm, double* __restrict__ heat,
                                                               unsigned long long* __restrict__ ctr64, int* __restrict__ ovoff,
                                                               int* __restrict__ heavy_list, unsigned* __restrict__ skey,
-                                                              double* __restrict__ sval, const int* __restrict__ hdr) {
+                                                              double* __restrict__ sval, const int* __restrict__ hdr, long wsz) {
+    hdr = zslice(hdr, wsz);
     if (!hough_gave_up(hdr)) return;
+    cnt = zslice(cnt, wsz); ink = zslice(ink, wsz); inv = zslice(inv, wsz); heat = zslice(heat, wsz); ctr64 = zslice(ctr64, wsz);
+    ovoff = zslice(ovoff, wsz); heavy_list = zslice(heavy_list, wsz); skey = zslice(skey, wsz); sval = zslice(sval, wsz);
     __shared__ int s_need[1024], s_hv[1024];
     __shared__ unsigned long long s_base;
     const int cc = blockIdx.x * 1024 + threadIdx.x;
@@ -205,8 +222,11 @@ __global__ __launch_bounds__(1024) void hough_classify_kernel(int ncells, const 
 }
 __global__ void hough_ovfill_kernel(long nvotes, int HW4, const int* __restrict__ ovcell, const double* __restrict__ ovval,
                                     const int* __restrict__ ovoff, int* __restrict__ ovcur, unsigned* __restrict__ skey,
-                                    double* __restrict__ sval, const int* __restrict__ hdr) {
+                                    double* __restrict__ sval, const int* __restrict__ hdr, long wsz) {
+    hdr = zslice(hdr, wsz);
     if (!hough_gave_up(hdr)) return;
+    ovcell = zslice(ovcell, wsz); ovval = zslice(ovval, wsz); ovoff = zslice(ovoff, wsz); ovcur = zslice(ovcur, wsz);
+    skey = zslice(skey, wsz); sval = zslice(sval, wsz);
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < nvotes; i += (long)gridDim.x * blockDim.x) {
         const int cc = ovcell[i];
         if (cc < 0) continue;
@@ -219,8 +239,11 @@ __global__ __launch_bounds__(64) void hough_heavy2_kernel(const int* __restrict_
                                                           const unsigned* __restrict__ skey, const double* __restrict__ sval,
                                                           double* __restrict__ srt, double norm, double* __restrict__ heat,
                                                           const unsigned long long* __restrict__ ctr64, const int* __restrict__ heavy_list,
-                                                          const int* __restrict__ hdr) {
+                                                          const int* __restrict__ hdr, long wsz) {
+    hdr = zslice(hdr, wsz);
     if (!hough_gave_up(hdr)) return;
+    cnt = zslice(cnt, wsz); ovoff = zslice(ovoff, wsz); skey = zslice(skey, wsz); sval = zslice(sval, wsz); srt = zslice(srt, wsz);
+    heat = zslice(heat, wsz); ctr64 = zslice(ctr64, wsz); heavy_list = zslice(heavy_list, wsz);
     __shared__ unsigned lk[HOUGH_LCAP];
     __shared__ double lv[HOUGH_LCAP];
     const int nh = (int)(unsigned)(*ctr64 >> 32);
@@ -287,8 +310,10 @@ __device__ __forceinline__ bool hough_is_far(int y, int x, int I, int J) {
 }
 __global__ __launch_bounds__(256) void hough_far_kernel(const float* __restrict__ kp, const float* __restrict__ soff, int H, int W, int* __restrict__ hdr,
                                                         int* __restrict__ farcell, unsigned* __restrict__ farkey, double* __restrict__ farval,
-                                                        int4* __restrict__ clr, long clr_n4) {
+                                                        int4* __restrict__ clr, long clr_n4, long wsz) {
     const int c = blockIdx.y, HW = H * W;
+    kp += (long)blockIdx.z * 5 * HW; soff += (long)blockIdx.z * 10 * HW;
+    hdr = zslice(hdr, wsz); farcell = zslice(farcell, wsz); farkey = zslice(farkey, wsz); farval = zslice(farval, wsz); clr = zslice(clr, wsz);
     // (also: zero the vote counters / slab cursors of the scatter formulation, should the tile formulation give up -- 15 HW bytes, no launch of its own)
     for (long i = ((long)blockIdx.y * gridDim.x + blockIdx.x) * blockDim.x + threadIdx.x; i < clr_n4; i += (long)gridDim.x * gridDim.y * blockDim.x)
         clr[i] = make_int4(0, 0, 0, 0);
@@ -307,7 +332,10 @@ __global__ __launch_bounds__(256) void hough_far_kernel(const float* __restrict_
 }
 __global__ __launch_bounds__(1024) void hough_tile_kernel(const float* __restrict__ kp, const float* __restrict__ soff, int H, int W, double norm,
                                                           double* __restrict__ heat, int* __restrict__ hdr, const int* __restrict__ farcell,
-                                                          const unsigned* __restrict__ farkey, const double* __restrict__ farval, int tiles_x) {
+                                                          const unsigned* __restrict__ farkey, const double* __restrict__ farval, int tiles_x,
+                                                          long wsz) {
+    kp += (long)blockIdx.z * 5 * H * W; soff += (long)blockIdx.z * 10 * H * W;
+    heat = zslice(heat, wsz); hdr = zslice(hdr, wsz); farcell = zslice(farcell, wsz); farkey = zslice(farkey, wsz); farval = zslice(farval, wsz);
     extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
     int* cnt = reinterpret_cast<int*>(sm);
     int* off = cnt + 1024;
@@ -441,9 +469,15 @@ __global__ __launch_bounds__(1024) void hough_tile_kernel(const float* __restric
     }
 }
 // start of the scatter formulation when the tile formulation gave up (hdr[1] | hdr[2] != 0): clears the slab allocator, the vote counters and the cursors
-__global__ void hough_clear_kernel(const int* __restrict__ hdr, int4* __restrict__ a, long n4) {
+__global__ void hough_clear_kernel(const int* __restrict__ hdr, int4* __restrict__ a, long n4, long wsz) {
+    hdr = zslice(hdr, wsz); a = zslice(a, wsz);
     if (!hough_gave_up(hdr)) return;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) a[i] = make_int4(0, 0, 0, 0);
+}
+// the 256-byte header of every image's workspace slice (one workgroup per image, one int per lane): zero, and hdr[1] = gave_up (hdr = header + 8)
+__global__ __launch_bounds__(64) void pp_header_init_kernel(int* __restrict__ header, long wsz, int gave_up) {
+    int* h = reinterpret_cast<int*>(reinterpret_cast<uintptr_t>(header) + (uintptr_t)((long)blockIdx.x * wsz));
+    h[threadIdx.x] = threadIdx.x == 9 ? gave_up : 0;
 }
 
 // ---- P2 ---------------------------------------------------------------------------------------
@@ -461,7 +495,8 @@ __device__ __forceinline__ int reflect_idx(int i, int n) {
     return i;
 }
 template <int AXIS>  // 0: along y (rows), 1: along x
-__global__ void gauss_kernel(const double* __restrict__ in, double* __restrict__ out, int C, int H, int W) {
+__global__ void gauss_kernel(const double* __restrict__ in, double* __restrict__ out, int C, int H, int W, long wsz) {
+    in = zslice(in, wsz); out = zslice(out, wsz);
     const long total = (long)C * H * W;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int x = (int)(i % W); const long q = i / W; const int y = (int)(q % H); const long c = q / H;
@@ -493,7 +528,10 @@ template <int PASS>
 __global__ __launch_bounds__(256) void peaks_kernel(const double* __restrict__ heat, int H, int W, double thresh,
                                                     int* __restrict__ blockcount, const int* __restrict__ blockbase,
                                                     int cap, int* __restrict__ ids, int* __restrict__ xs,
-                                                    int* __restrict__ ys, double* __restrict__ conf) {
+                                                    int* __restrict__ ys, double* __restrict__ conf, long wsz) {
+    heat = zslice(heat, wsz);
+    if (PASS == 0) blockcount = zslice(blockcount, wsz);
+    else { blockbase = zslice(blockbase, wsz); ids = zslice(ids, wsz); xs = zslice(xs, wsz); ys = zslice(ys, wsz); conf = zslice(conf, wsz); }
     const long HW = (long)H * W, total = 5 * HW;
     const long i0 = (long)blockIdx.x * 1024 + threadIdx.x * 4;  // 4 consecutive elements per thread
     bool f[4]; int cnt = 0;
@@ -542,7 +580,9 @@ __device__ __forceinline__ double norm2(double dx, double dy) { return sqrt(fma(
 __global__ void kp_rank_kernel(const int* __restrict__ npk, int cap, const int* __restrict__ ids,
                                const int* __restrict__ xs, const int* __restrict__ ys, const double* __restrict__ conf,
                                int* __restrict__ sid, int* __restrict__ sx, int* __restrict__ sy,
-                               double* __restrict__ sconf) {
+                               double* __restrict__ sconf, long wsz) {
+    npk = zslice(npk, wsz); ids = zslice(ids, wsz); xs = zslice(xs, wsz); ys = zslice(ys, wsz); conf = zslice(conf, wsz);
+    sid = zslice(sid, wsz); sx = zslice(sx, wsz); sy = zslice(sy, wsz); sconf = zslice(sconf, wsz);
     // Rank of peak i = number of peaks that precede it in the stable descending order.  16 lanes share a peak (lane = every 16th
     // candidate of a 256-entry LDS tile), their partial counts meet through four shuffles: the fp64 compares are the cost of this
     // kernel (as one thread per peak over global memory the c0 map of a 512 x 512 image -- ~8000 peaks -- took 105-120 us).
@@ -713,8 +753,11 @@ __global__ __launch_bounds__(256) void group_kernel(const int* __restrict__ npk,
                                                     const double* __restrict__ sconf, const float* __restrict__ mid,
                                                     int H, int W, unsigned char* __restrict__ alive, int skcap,
                                                     int* __restrict__ skxy, double* __restrict__ skel,
-                                                    int* __restrict__ nskel) {
+                                                    int* __restrict__ nskel, long wsz) {
     // skxy[s][5][2]: integer slot coordinates of skeleton s (missing slot = (0,0)) for the <=10 test
+    npk = zslice(npk, wsz); sid = zslice(sid, wsz); sx = zslice(sx, wsz); sy = zslice(sy, wsz); sconf = zslice(sconf, wsz);
+    alive = zslice(alive, wsz); skxy = zslice(skxy, wsz);
+    mid += (long)blockIdx.z * 40 * H * W; skel += (long)blockIdx.z * skcap * 15; nskel += blockIdx.z;     // (outputs [N][skcap][5][3], [N])
     int n = *npk; if (n > cap) n = cap;
     extern __shared__ __attribute__((aligned(16))) unsigned char group_smem[];
     if (n <= GK_NL && H <= 1024 && W <= 1024) {      // (the general path below serves larger inputs)
@@ -817,44 +860,66 @@ __device__ int skeleton_box(const double* __restrict__ sk_in, double scale, int 
     box[0] = y1; box[1] = x1; box[2] = y2; box[3] = x2; box[4] = sum / (double)cnt;
     return 1;
 }
-// one block; appends the boxes of this scale after the *nbox already present (order preserved)
-__global__ __launch_bounds__(1024) void boxes_kernel(const int* __restrict__ nskel, int skcap,
-                                                     const double* __restrict__ skel, double scale, int do_refine,
-                                                     int boxcap, double* __restrict__ boxes, int* __restrict__ nbox) {
+// the scales of one box assembly: skel[s] [N][cap[s]][5][3], nskel[s] [N]
+#define KG_MAX_SCALES 4
+struct BoxScales {
+    const double* skel[KG_MAX_SCALES];
+    const int* nskel[KG_MAX_SCALES];
+    int cap[KG_MAX_SCALES];
+    double scale[KG_MAX_SCALES];
+    int n;
+};
+// one block per image; appends the boxes of its scales in order (order preserved within each) to boxes [N][boxcap][5], after the nbox[img]
+// already present (append) or from 0.  nbox[img] = boxes produced (may exceed boxcap: the excess is dropped, as nms_kernel clamps).
+__global__ __launch_bounds__(1024) void boxes_kernel(BoxScales S, int do_refine, int append, int boxcap, double* __restrict__ boxes,
+                                                     int* __restrict__ nbox) {
     __shared__ int sc[1024];
     __shared__ int s_base;
-    int n = *nskel; if (n > skcap) n = skcap;
-    if (threadIdx.x == 0) s_base = *nbox;
+    const int img = blockIdx.x;
+    boxes += (long)img * boxcap * 5; nbox += img;
+    if (threadIdx.x == 0) s_base = append ? *nbox : 0;
     __syncthreads();
-    for (int c0 = 0; c0 < n; c0 += 1024) {
-        const int i = c0 + threadIdx.x;
-        double b[5]; int ok = 0;
-        if (i < n) ok = skeleton_box(skel + (long)i * 15, scale, do_refine, b);
-        sc[threadIdx.x] = ok;
-        __syncthreads();
-        for (int d = 1; d < 1024; d <<= 1) {
-            int v = threadIdx.x >= d ? sc[threadIdx.x - d] : 0;
+    for (int s = 0; s < S.n; ++s) {
+        const int skcap = S.cap[s];
+        const double* skel = S.skel[s] + (long)img * skcap * 15;
+        const double scale = S.scale[s];
+        int n = S.nskel[s][img]; if (n > skcap) n = skcap;
+        for (int c0 = 0; c0 < n; c0 += 1024) {
+            const int i = c0 + threadIdx.x;
+            double b[5]; int ok = 0;
+            if (i < n) ok = skeleton_box(skel + (long)i * 15, scale, do_refine, b);
+            sc[threadIdx.x] = ok;
             __syncthreads();
-            sc[threadIdx.x] += v;
+            for (int d = 1; d < 1024; d <<= 1) {
+                int v = threadIdx.x >= d ? sc[threadIdx.x - d] : 0;
+                __syncthreads();
+                sc[threadIdx.x] += v;
+                __syncthreads();
+            }
+            const int pos = s_base + sc[threadIdx.x] - ok;
+            if (ok && pos < boxcap)
+                for (int q = 0; q < 5; ++q) boxes[(long)pos * 5 + q] = b[q];
+            __syncthreads();
+            if (threadIdx.x == 1023) s_base += sc[1023];
             __syncthreads();
         }
-        const int pos = s_base + sc[threadIdx.x] - ok;
-        if (ok && pos < boxcap)
-            for (int q = 0; q < 5; ++q) boxes[(long)pos * 5 + q] = b[q];
-        __syncthreads();
-        if (threadIdx.x == 1023) s_base += sc[1023];
-        __syncthreads();
     }
     if (threadIdx.x == 0) *nbox = s_base;
 }
 
 // ---- P9 ---------------------------------------------------------------------------------------
 #define NMS_NL 2048
-// one block.  order[] = indices sorted by confidence ascending (ties: index ascending).
+// one block per image (boxes [N][boxcap][5], nbox / nkeep [N], order / dead / keep in the image's workspace slice of wsz bytes).
+// order[] = indices sorted by confidence ascending (ties: index ascending).
 __global__ __launch_bounds__(1024) void nms_kernel(const int* __restrict__ nbox, int boxcap,
                                                    const double* __restrict__ boxes, double thresh,
                                                    int* __restrict__ order, unsigned char* __restrict__ dead,
-                                                   int* __restrict__ keep, int* __restrict__ nkeep) {
+                                                   int* __restrict__ keep, int* __restrict__ nkeep, long wsz) {
+    const int img = blockIdx.x;
+    const long wo = (long)img * wsz;
+    nbox += img; nkeep += img; boxes += (long)img * boxcap * 5;
+    order = reinterpret_cast<int*>(reinterpret_cast<uintptr_t>(order) + wo); keep = reinterpret_cast<int*>(reinterpret_cast<uintptr_t>(keep) + wo);
+    dead += wo;
     int n = *nbox; if (n > boxcap) n = boxcap;
     for (int i = threadIdx.x; i < n; i += 1024) {
         const double ci = boxes[(long)i * 5 + 4];
@@ -926,9 +991,15 @@ __global__ __launch_bounds__(1024) void nms_kernel(const int* __restrict__ nbox,
     }
     if (threadIdx.x == 0) *nkeep = nk;
 }
-__global__ void gather_rows5_kernel(const double* __restrict__ boxes, const int* __restrict__ keep,
+// kept boxes of image blockIdx.y, in pick order, at row sum(nkeep[0 .. img)) of the compact out [sum nkeep][5]
+__global__ void gather_rows5_kernel(const double* __restrict__ boxes, int boxcap, const int* __restrict__ keep, long wsz,
                                     const int* __restrict__ nkeep, double* __restrict__ out) {
-    int n = *nkeep;
+    const int img = blockIdx.y;
+    long row0 = 0;
+    for (int j = 0; j < img; ++j) row0 += nkeep[j];
+    boxes += (long)img * boxcap * 5; out += row0 * 5;
+    keep = reinterpret_cast<const int*>(reinterpret_cast<uintptr_t>(keep) + (uintptr_t)((long)img * wsz));
+    int n = nkeep[img];
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n * 5; i += gridDim.x * blockDim.x)
         out[i] = boxes[(long)keep[i / 5] * 5 + (i % 5)];
 }
@@ -1021,104 +1092,157 @@ extern "C" int kg_postproc_timing_end(float* ms4) {
     return KG_OK;
 }
 
-// P1..P4 for one scale (batch element 0 of the maps).  kp [5][H][W], soff [10][H][W], mid [40][H][W] fp32
-// device pointers.  Outputs (device): skel [skel_cap][5][3] f64, nskel, and optionally copies of the
-// intermediate stages (heat_out/blur_out [5][H][W] f64, peaks) for parity tests.
-extern "C" int kg_postproc_scale(const float* kp, const float* soff, const float* mid, int H, int W, double thresh,
-                                 void* ws, long ws_bytes, int peak_cap, int skel_cap, double* skel, int* nskel,
-                                 double* heat_out, double* blur_out, int* peaks_out, double* peak_conf_out,
-                                 int* npeaks_out, void* stream) {
-    KG_CHECK_ARG(kp && soff && mid && ws && skel && nskel, "kg_postproc_scale: null pointer");
-    KG_CHECK_ARG(H >= 1 && W >= 1 && (long)H * W <= (1L << 28) / 4, "kg_postproc_scale: bad size");
-    KG_CHECK_ARG(W < 65536 && H < 65536, "kg_postproc_scale: map too large");
-    KG_CHECK_ARG(ws_bytes >= kg_postproc_workspace_bytes(H, W, peak_cap, skel_cap), "kg_postproc_scale: workspace too small");
+// P1..P4 of one scale for N images.  kp [N][5][H][W], soff [N][10][H][W], mid [N][40][H][W] fp32 device pointers; ws holds N slices of
+// wsz bytes (one image's workspace each).  Outputs (device): skel [N][skel_cap][5][3] f64, nskel [N], and for N == 1 optionally copies of
+// the intermediate stages (heat_out/blur_out [5][H][W] f64, peaks) for parity tests.
+static int postproc_launch(const char* who, const float* kp, const float* soff, const float* mid, int N, int H, int W, double thresh,
+                           void* ws, long ws_bytes, int peak_cap, int skel_cap, double* skel, int* nskel, double* heat_out,
+                           double* blur_out, int* peaks_out, double* peak_conf_out, int* npeaks_out, void* stream) {
+    KG_CHECK_ARG(kp && soff && mid && ws && skel && nskel, "%s: null pointer", who);
+    KG_CHECK_ARG(N >= 1 && N <= 65535, "%s: bad image count %d", who, N);
+    KG_CHECK_ARG(H >= 1 && W >= 1 && (long)H * W <= (1L << 28) / 4, "%s: bad size", who);
+    KG_CHECK_ARG(W < 65536 && H < 65536, "%s: map too large", who);
+    KG_CHECK_ARG(peak_cap >= 1 && skel_cap >= 1, "%s: bad capacities", who);
+    const long wsz = kg_postproc_workspace_bytes(H, W, peak_cap, skel_cap);      // (a multiple of 256: every term of the sum is)
+    KG_CHECK_ARG(ws_bytes >= wsz * N, "%s: workspace too small", who);
     hipStream_t st = (hipStream_t)stream;
-    PPWs p; carve(ws, H, W, peak_cap, skel_cap, &p);
+    PPWs p; carve(ws, H, W, peak_cap, skel_cap, &p);      // image 0's slice; the kernels add blockIdx.z * wsz
     const int HW = H * W;
     const double norm = 3.141592653589793 * 25.0;  // np.pi * KP_RADIUS**2 (postprocessing.py:51)
+    // the early-exit launches of the scatter formulation (grid-stride loops) get 1/N of their workgroups per image: a batch of images that all
+    // keep the tile formulation dispatches about as many empty workgroups as one image did
+    auto per_img = [N](int g) { const int q = g / N; return N == 1 ? g : q < 64 ? 64 : q; };
     pp_mark(st);
     int gx = (4 * HW + 255) / 256; if (gx > 2048) gx = 2048;
     {
-        // header (p.heavy_n, 256 bytes): [0..1] the 64-bit slab allocator of the scatter formulation, [8] = far-vote count, [9] / [10] = "tile formulation
-        // gave up" flags (far-list overflow / tile overflow; hdr = &heavy_n[8]).  KG_HOUGH_TILE=0: scatter formulation only.
+        // header (p.heavy_n, 256 bytes per image): [0..1] the 64-bit slab allocator of the scatter formulation, [8] = far-vote count, [9] / [10] =
+        // "tile formulation gave up" flags (far-list overflow / tile overflow; hdr = &heavy_n[8]).  KG_HOUGH_TILE=0: scatter formulation only.
         static const int use_tile = getenv("KG_HOUGH_TILE") ? atoi(getenv("KG_HOUGH_TILE")) : 1;
         int* hdr = p.heavy_n + 8;
         const long clr = (long)(((unsigned char*)p.cursor - (unsigned char*)p.count) + (size_t)5 * HW * 4 + 15) / 16;      // (rounded UP: the al256 padding behind `cursor` takes the 1-3 extra ints)
-        KG_HIP(hipMemsetAsync(p.heavy_n, 0, 256, st));
+        hipLaunchKernelGGL(pp_header_init_kernel, dim3(N), dim3(64), 0, st, p.heavy_n, wsz, use_tile ? 0 : 1);
         if (use_tile) {
             // far list in the scatter formulation's (then unused) arrays: cells in `sorted`, keys in `keys`, values in `vals`
             int* farcell = reinterpret_cast<int*>(p.sorted);
             int gf = (HW + 255) / 256; if (gf > 2048) gf = 2048;
-            hipLaunchKernelGGL(hough_far_kernel, dim3(gf, 5), dim3(256), 0, st, kp, soff, H, W, hdr, farcell, p.keys, p.vals, reinterpret_cast<int4*>(p.count), clr);
+            hipLaunchKernelGGL(hough_far_kernel, dim3(gf, 5, N), dim3(256), 0, st, kp, soff, H, W, hdr, farcell, p.keys, p.vals,
+                               reinterpret_cast<int4*>(p.count), clr, wsz);
             constexpr int tile_lds = 3 * 1024 * 4 + HT_CAP * 4 + HT_CAP * 8 + 16 * HT_SCR * 8;
             static KgPerDevice tile_attr;
             if (tile_attr.first()) {
                 KG_HIP(hipFuncSetAttribute((const void*)hough_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, tile_lds));
             }
             const int tiles_x = (W + HT_T - 1) / HT_T, tiles_y = (H + HT_T - 1) / HT_T;
-            hipLaunchKernelGGL(hough_tile_kernel, dim3(tiles_x * tiles_y, 5), dim3(1024), tile_lds, st, kp, soff, H, W, norm, p.heat, hdr, farcell, p.keys,
-                               p.vals, tiles_x);
+            hipLaunchKernelGGL(hough_tile_kernel, dim3(tiles_x * tiles_y, 5, N), dim3(1024), tile_lds, st, kp, soff, H, W, norm, p.heat, hdr, farcell,
+                               p.keys, p.vals, tiles_x, wsz);
         } else {
-            KG_HIP(hipMemsetD32Async((hipDeviceptr_t)(hdr + 1), 1, 1, st));
-            hipLaunchKernelGGL(hough_clear_kernel, dim3(1024), dim3(256), 0, st, hdr, reinterpret_cast<int4*>(p.count), clr);
+            hipLaunchKernelGGL(hough_clear_kernel, dim3(1024, 1, N), dim3(256), 0, st, hdr, reinterpret_cast<int4*>(p.count), clr, wsz);
         }
         // scatter formulation, every kernel a no-op while hdr[1] | hdr[2] == 0 (its counters count | offs | cursor were cleared by the far pass)
         unsigned long long* ctr64 = reinterpret_cast<unsigned long long*>(p.heavy_n);
-        hipLaunchKernelGGL(hough_scatter_kernel, dim3(gx, 5), dim3(256), 0, st, kp, soff, H, W, p.count, p.ink, p.inv, (int*)p.keys, p.vals, hdr);
-        hipLaunchKernelGGL(hough_classify_kernel, dim3((5 * HW + 1023) / 1024), dim3(1024), 0, st, 5 * HW, p.count, p.ink, p.inv, norm, p.heat, ctr64,
-                           p.offs, p.heavy_list, p.skey, p.sorted, hdr);
+        hipLaunchKernelGGL(hough_scatter_kernel, dim3(per_img(gx), 5, N), dim3(256), 0, st, kp, soff, H, W, p.count, p.ink, p.inv, (int*)p.keys,
+                           p.vals, hdr, wsz);
+        hipLaunchKernelGGL(hough_classify_kernel, dim3((5 * HW + 1023) / 1024, 1, N), dim3(1024), 0, st, 5 * HW, p.count, p.ink, p.inv, norm, p.heat,
+                           ctr64, p.offs, p.heavy_list, p.skey, p.sorted, hdr, wsz);
         int go = (int)(((long)20 * HW + 255) / 256); if (go > 4096) go = 4096;
-        hipLaunchKernelGGL(hough_ovfill_kernel, dim3(go), dim3(256), 0, st, (long)20 * HW, 4 * HW, (const int*)p.keys, p.vals, p.offs, p.cursor, p.skey,
-                           p.sorted, hdr);
-        hipLaunchKernelGGL(hough_heavy2_kernel, dim3(4096), dim3(64), 0, st, p.count, p.offs, p.skey, p.sorted, p.srt, norm, p.heat, ctr64, p.heavy_list, hdr);
+        hipLaunchKernelGGL(hough_ovfill_kernel, dim3(per_img(go), 1, N), dim3(256), 0, st, (long)20 * HW, 4 * HW, (const int*)p.keys, p.vals, p.offs,
+                           p.cursor, p.skey, p.sorted, hdr, wsz);
+        hipLaunchKernelGGL(hough_heavy2_kernel, dim3(per_img(4096), 1, N), dim3(64), 0, st, p.count, p.offs, p.skey, p.sorted, p.srt, norm, p.heat,
+                           ctr64, p.heavy_list, hdr, wsz);
     }
     int gg = (5 * HW + 255) / 256; if (gg > 8192) gg = 8192;
     pp_mark(st);
-    hipLaunchKernelGGL(gauss_kernel<0>, dim3(gg), dim3(256), 0, st, p.heat, p.tmp, 5, H, W);
-    hipLaunchKernelGGL(gauss_kernel<1>, dim3(gg), dim3(256), 0, st, p.tmp, p.blur, 5, H, W);
+    hipLaunchKernelGGL(gauss_kernel<0>, dim3(gg, 1, N), dim3(256), 0, st, p.heat, p.tmp, 5, H, W, wsz);
+    hipLaunchKernelGGL(gauss_kernel<1>, dim3(gg, 1, N), dim3(256), 0, st, p.tmp, p.blur, 5, H, W, wsz);
     pp_mark(st);
-    hipLaunchKernelGGL(peaks_kernel<0>, dim3(p.nblk), dim3(256), 0, st, p.blur, H, W, thresh, p.blkcount, (const int*)nullptr, 0,
-                       (int*)nullptr, (int*)nullptr, (int*)nullptr, (double*)nullptr);
-    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, st, p.blkcount, p.blkbase, p.nblk, p.npk);
-    hipLaunchKernelGGL(peaks_kernel<1>, dim3(p.nblk), dim3(256), 0, st, p.blur, H, W, thresh, (int*)nullptr, p.blkbase, peak_cap,
-                       p.ids, p.xs, p.ys, p.conf);
-    hipLaunchKernelGGL(kp_rank_kernel, dim3(512), dim3(256), 0, st, p.npk, peak_cap, p.ids, p.xs, p.ys, p.conf, p.sid, p.sx, p.sy,
-                       p.sconf);
+    hipLaunchKernelGGL(peaks_kernel<0>, dim3(p.nblk, 1, N), dim3(256), 0, st, p.blur, H, W, thresh, p.blkcount, (const int*)nullptr, 0,
+                       (int*)nullptr, (int*)nullptr, (int*)nullptr, (double*)nullptr, wsz);
+    hipLaunchKernelGGL(scan_kernel, dim3(1, 1, N), dim3(1024), 0, st, p.blkcount, p.blkbase, p.nblk, p.npk, wsz);
+    hipLaunchKernelGGL(peaks_kernel<1>, dim3(p.nblk, 1, N), dim3(256), 0, st, p.blur, H, W, thresh, (int*)nullptr, p.blkbase, peak_cap,
+                       p.ids, p.xs, p.ys, p.conf, wsz);
+    hipLaunchKernelGGL(kp_rank_kernel, dim3(512, 1, N), dim3(256), 0, st, p.npk, peak_cap, p.ids, p.xs, p.ys, p.conf, p.sid, p.sx, p.sy,
+                       p.sconf, wsz);
     pp_mark(st);
     static KgPerDevice group_attr;
     if (group_attr.first()) {
         KG_HIP(hipFuncSetAttribute((const void*)group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(GroupLds)));
     }
-    hipLaunchKernelGGL(group_kernel, dim3(1), dim3(256), sizeof(GroupLds), st, p.npk, peak_cap, p.sid, p.sx, p.sy, p.sconf, mid, H, W, p.alive,
-                       skel_cap, p.skxy, skel, nskel);
+    hipLaunchKernelGGL(group_kernel, dim3(1, 1, N), dim3(256), sizeof(GroupLds), st, p.npk, peak_cap, p.sid, p.sx, p.sy, p.sconf, mid, H, W,
+                       p.alive, skel_cap, p.skxy, skel, nskel, wsz);
     pp_mark(st);
-    if (heat_out) KG_HIP(hipMemcpyAsync(heat_out, p.heat, (size_t)5 * HW * 8, hipMemcpyDeviceToDevice, st));
-    if (blur_out) KG_HIP(hipMemcpyAsync(blur_out, p.blur, (size_t)5 * HW * 8, hipMemcpyDeviceToDevice, st));
-    if (npeaks_out) KG_HIP(hipMemcpyAsync(npeaks_out, p.npk, 4, hipMemcpyDeviceToDevice, st));
-    if (peaks_out) {
-        KG_HIP(hipMemcpyAsync(peaks_out, p.ids, (size_t)peak_cap * 4, hipMemcpyDeviceToDevice, st));
-        KG_HIP(hipMemcpyAsync(peaks_out + peak_cap, p.xs, (size_t)peak_cap * 4, hipMemcpyDeviceToDevice, st));
-        KG_HIP(hipMemcpyAsync(peaks_out + 2 * (size_t)peak_cap, p.ys, (size_t)peak_cap * 4, hipMemcpyDeviceToDevice, st));
+    if (N == 1) {
+        if (heat_out) KG_HIP(hipMemcpyAsync(heat_out, p.heat, (size_t)5 * HW * 8, hipMemcpyDeviceToDevice, st));
+        if (blur_out) KG_HIP(hipMemcpyAsync(blur_out, p.blur, (size_t)5 * HW * 8, hipMemcpyDeviceToDevice, st));
+        if (npeaks_out) KG_HIP(hipMemcpyAsync(npeaks_out, p.npk, 4, hipMemcpyDeviceToDevice, st));
+        if (peaks_out) {
+            KG_HIP(hipMemcpyAsync(peaks_out, p.ids, (size_t)peak_cap * 4, hipMemcpyDeviceToDevice, st));
+            KG_HIP(hipMemcpyAsync(peaks_out + peak_cap, p.xs, (size_t)peak_cap * 4, hipMemcpyDeviceToDevice, st));
+            KG_HIP(hipMemcpyAsync(peaks_out + 2 * (size_t)peak_cap, p.ys, (size_t)peak_cap * 4, hipMemcpyDeviceToDevice, st));
+        }
+        if (peak_conf_out) KG_HIP(hipMemcpyAsync(peak_conf_out, p.conf, (size_t)peak_cap * 8, hipMemcpyDeviceToDevice, st));
     }
-    if (peak_conf_out) KG_HIP(hipMemcpyAsync(peak_conf_out, p.conf, (size_t)peak_cap * 8, hipMemcpyDeviceToDevice, st));
-    KG_CHECK_LAUNCH("postproc_scale");
+    KG_CHECK_LAUNCH(who);
     return KG_OK;
 }
 
+// P1..P4 for one scale (batch element 0 of the maps): the N = 1 case of postproc_launch, with its optional stage copies.
+extern "C" int kg_postproc_scale(const float* kp, const float* soff, const float* mid, int H, int W, double thresh,
+                                 void* ws, long ws_bytes, int peak_cap, int skel_cap, double* skel, int* nskel,
+                                 double* heat_out, double* blur_out, int* peaks_out, double* peak_conf_out,
+                                 int* npeaks_out, void* stream) {
+    return postproc_launch("kg_postproc_scale", kp, soff, mid, 1, H, W, thresh, ws, ws_bytes, peak_cap, skel_cap, skel, nskel, heat_out,
+                           blur_out, peaks_out, peak_conf_out, npeaks_out, stream);
+}
+
+extern "C" long kg_postproc_batch_workspace_bytes(int N, int H, int W, int peak_cap, int skel_cap) {
+    if (N < 1 || H < 1 || W < 1) { kg_set_error("kg_postproc_batch_workspace_bytes: bad arguments"); return -1; }
+    return (long)N * kg_postproc_workspace_bytes(H, W, peak_cap, skel_cap);
+}
+
+// P1..P4 for one scale of N images: one launch per stage for all of them.
+extern "C" int kg_postproc_batch(const float* kp, const float* soff, const float* mid, int N, int H, int W, double thresh, void* ws,
+                                 long ws_bytes, int peak_cap, int skel_cap, double* skel, int* nskel, void* stream) {
+    return postproc_launch("kg_postproc_batch", kp, soff, mid, N, H, W, thresh, ws, ws_bytes, peak_cap, skel_cap, skel, nskel, nullptr,
+                           nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+// P6+P7: boxes of nscales scales of N images, one workgroup per image.  skel / nskel / skel_cap / scale: HOST arrays of nscales entries.
+static int boxes_launch(const char* who, int N, int nscales, const double* const* skel, const int* const* nskel, const int* skel_cap,
+                        const double* scale, int do_refine, int append, double* boxes, int* nbox, int box_cap, void* stream) {
+    KG_CHECK_ARG(N >= 1 && nscales >= 1 && nscales <= KG_MAX_SCALES, "%s: bad image / scale count", who);
+    KG_CHECK_ARG(skel && nskel && skel_cap && scale && boxes && nbox && box_cap >= 1, "%s: null pointer or bad capacity", who);
+    BoxScales S = {};
+    S.n = nscales;
+    for (int s = 0; s < nscales; ++s) {
+        KG_CHECK_ARG(skel[s] && nskel[s] && skel_cap[s] >= 1, "%s: null pointer or bad capacity (scale %d)", who, s);
+        S.skel[s] = skel[s]; S.nskel[s] = nskel[s]; S.cap[s] = skel_cap[s]; S.scale[s] = scale[s];
+    }
+    hipLaunchKernelGGL(boxes_kernel, dim3(N), dim3(1024), 0, (hipStream_t)stream, S, do_refine, append, box_cap, boxes, nbox);
+    KG_CHECK_LAUNCH(who);
+    return KG_OK;
+}
 // P6+P7: append boxes of one scale's skeletons to boxes[] (nbox is read-modify-written on device).
 extern "C" int kg_skeleton_boxes(const double* skel, const int* nskel, int skel_cap, double scale, int do_refine,
                                  double* boxes, int* nbox, int box_cap, void* stream) {
-    KG_CHECK_ARG(skel && nskel && boxes && nbox, "kg_skeleton_boxes: null pointer");
-    hipLaunchKernelGGL(boxes_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, nskel, skel_cap, skel, scale, do_refine, box_cap,
-                       boxes, nbox);
-    KG_CHECK_LAUNCH("skeleton_boxes");
-    return KG_OK;
+    return boxes_launch("kg_skeleton_boxes", 1, 1, &skel, &nskel, &skel_cap, &scale, do_refine, 1, boxes, nbox, box_cap, stream);
 }
-// P9: ws needs box_cap*(4+1+4) bytes (+ alignment).  out [box_cap][5] kept boxes in pick order.
-extern "C" int kg_nms(const double* boxes, const int* nbox, int box_cap, double thresh, void* ws, long ws_bytes,
+extern "C" int kg_skeleton_boxes_batch(int N, int nscales, const double* const* skel, const int* const* nskel, const int* skel_cap,
+                                       const double* scale, int do_refine, double* boxes, int* nbox, int box_cap, void* stream) {
+    return boxes_launch("kg_skeleton_boxes_batch", N, nscales, skel, nskel, skel_cap, scale, do_refine, 0, boxes, nbox, box_cap, stream);
+}
+
+// P9: per image, ws needs box_cap*(4+1+4) bytes (+ alignment).  out: kept boxes of all images in pick order, image after image.
+static long nms_ws_one(int box_cap) { return (long)(al256((size_t)box_cap * 4) * 2 + al256(box_cap)); }
+extern "C" long kg_nms_batch_workspace_bytes(int N, int box_cap) {
+    if (N < 1 || box_cap < 1) { kg_set_error("kg_nms_batch_workspace_bytes: bad arguments"); return -1; }
+    return (long)N * nms_ws_one(box_cap);
+}
+static int nms_launch(const char* who, int N, const double* boxes, const int* nbox, int box_cap, double thresh, void* ws, long ws_bytes,
                       double* out, int* nkeep, void* stream) {
-    KG_CHECK_ARG(boxes && nbox && ws && out && nkeep, "kg_nms: null pointer");
-    KG_CHECK_ARG(ws_bytes >= (long)(al256((size_t)box_cap * 4) * 2 + al256(box_cap)), "kg_nms: workspace too small");
+    KG_CHECK_ARG(boxes && nbox && ws && out && nkeep, "%s: null pointer", who);
+    KG_CHECK_ARG(N >= 1 && N <= 65535 && box_cap >= 1, "%s: bad image count or capacity", who);
+    const long wsz = nms_ws_one(box_cap);
+    KG_CHECK_ARG(ws_bytes >= wsz * N, "%s: workspace too small", who);
     unsigned char* q = (unsigned char*)ws;
     int* order = (int*)q; q += al256((size_t)box_cap * 4);
     int* keep = (int*)q; q += al256((size_t)box_cap * 4);
@@ -1129,10 +1253,19 @@ extern "C" int kg_nms(const double* boxes, const int* nbox, int box_cap, double 
     if (nms_attr.first()) {
         KG_HIP(hipFuncSetAttribute((const void*)nms_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, nms_lds));
     }
-    hipLaunchKernelGGL(nms_kernel, dim3(1), dim3(1024), nms_lds, st, nbox, box_cap, boxes, thresh, order, dead, keep, nkeep);
-    hipLaunchKernelGGL(gather_rows5_kernel, dim3(64), dim3(256), 0, st, boxes, keep, nkeep, out);
-    KG_CHECK_LAUNCH("nms");
+    hipLaunchKernelGGL(nms_kernel, dim3(N), dim3(1024), nms_lds, st, nbox, box_cap, boxes, thresh, order, dead, keep, nkeep, wsz);
+    hipLaunchKernelGGL(gather_rows5_kernel, dim3(64, N), dim3(256), 0, st, boxes, box_cap, keep, wsz, nkeep, out);
+    KG_CHECK_LAUNCH(who);
     return KG_OK;
+}
+// P9: ws needs box_cap*(4+1+4) bytes (+ alignment).  out [box_cap][5] kept boxes in pick order.
+extern "C" int kg_nms(const double* boxes, const int* nbox, int box_cap, double thresh, void* ws, long ws_bytes,
+                      double* out, int* nkeep, void* stream) {
+    return nms_launch("kg_nms", 1, boxes, nbox, box_cap, thresh, ws, ws_bytes, out, nkeep, stream);
+}
+extern "C" int kg_nms_batch(int N, const double* boxes, const int* nbox, int box_cap, double thresh, void* ws, long ws_bytes,
+                            double* out, int* nkeep, void* stream) {
+    return nms_launch("kg_nms_batch", N, boxes, nbox, box_cap, thresh, ws, ws_bytes, out, nkeep, stream);
 }
 
 // fp64 primitive probe for the parity tests: out = {a/b, sqrt(|a|), fma(a,a,b*b), floor(a), ceil(a)}

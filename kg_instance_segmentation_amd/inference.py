@@ -1,0 +1,81 @@
+"""Batched inference: the reference driver's per-image evaluation path (test.py:88-157, test_inference + post_processing) for a whole
+batch of images in one call.
+
+    forward_dec over the batch -> detect_batch -> ONE forward_seg with every image's boxes -> one kg_mask_paste launch per output size.
+
+predict() is an opt-in API for a caller's own evaluation loop; the reference drivers (dropin/) are unchanged.  Resizing the source images
+to the network input stays with the caller."""
+import numpy as np
+import torch
+
+from . import _lib, postprocessing
+
+
+def image_row_ranges(img, nimg):
+    """[start, stop) of every image's rows in a flat list of rows sorted by image index (forward_seg's kg_meta["img"])."""
+    img = np.asarray(img, np.int64).reshape(-1)
+    if len(img) and np.any(np.diff(img) < 0):
+        raise _lib.KGLibraryError("image_row_ranges: rows are not sorted by image")
+    starts = np.searchsorted(img, np.arange(nimg + 1), side="left")
+    return [(int(starts[i]), int(starts[i + 1])) for i in range(nimg)]
+
+
+def size_groups(image_sizes):
+    """Images grouped by output size, in order of first appearance: [((h, w), [image indices])]."""
+    groups = {}
+    for i, hw in enumerate(image_sizes):
+        groups.setdefault((int(hw[0]), int(hw[1])), []).append(i)
+    return list(groups.items())
+
+
+def predict(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None, device_u8=False, max_workspace_bytes=None):
+    """test_inference + post_processing (test.py:88-157) for the batch x [N,3,H,W] (already resized and normalised as test.py:91-92 does).
+    The model's mode is left as it is.  image_sizes: (h, w) of every source image (default: the input size).
+    Returns N entries: None (no detection) or [masks float32 [n, h, w] in {0, 1}, dets float32 [n, 5] (y1, x1, y2, x2, conf) in image pixels],
+    the masks as uint8 device tensors with device_u8=True."""
+    with torch.no_grad():
+        d0, d1, d2, d3, feat_seg = model.forward_dec(x)
+    return predict_from_heads(model, [d0, d1, d2, d3], feat_seg, x.shape[2], x.shape[3], nms_thresh, seg_thresh, image_sizes, device_u8,
+                              max_workspace_bytes)
+
+
+def predict_from_heads(model, dec, feat_seg, input_h, input_w, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None, device_u8=False,
+                       max_workspace_bytes=None):
+    """The part of predict() after forward_dec: dec = ([kp, short, mid] x 4) and feat_seg of a batch, as forward_dec returns them."""
+    N = dec[0][0].shape[0]
+    sizes = [(int(input_h), int(input_w))] * N if image_sizes is None else [(int(h), int(w)) for h, w in image_sizes]
+    if len(sizes) != N:
+        raise _lib.KGLibraryError(f"predict: {len(sizes)} image sizes for {N} images")
+    dets = postprocessing.detect_batch(dec, nms_thresh, max_workspace_bytes=max_workspace_bytes)
+    if all(d is None for d in dets):
+        return [None] * N
+    boxes = [d if d is not None else np.zeros((0, 5), np.float64) for d in dets]   # (one array per image, as test.py:119 passes [bboxes])
+    with torch.no_grad():
+        pred = model.forward_seg(feat_seg, boxes)
+    meta = getattr(pred, "kg_meta", None)
+    out = [None] * N
+    if meta is None:                     # every box fell outside the feature maps: no mask rows at all
+        for i in range(N):
+            if dets[i] is not None:
+                out[i] = _empty(sizes[i], device_u8, feat_seg[0].device)
+        return out
+    rng = image_row_ranges(meta["img"], N)
+    off, hh, ww, bx = np.asarray(meta["off"]), np.asarray(meta["h"]), np.asarray(meta["w"]), np.asarray(meta["boxes"])
+    for (h, w), imgs in size_groups(sizes):
+        imgs = [i for i in imgs if dets[i] is not None]
+        if not imgs:
+            continue
+        sel = np.concatenate([np.arange(*rng[i]) for i in imgs]).astype(np.int64)
+        masks, d = postprocessing.paste_rows(meta["flat"], off[sel], hh[sel], ww[sel], bx[sel], input_h, input_w, w, h, seg_thresh, device_u8)
+        r = 0
+        for i in imgs:
+            k = rng[i][1] - rng[i][0]
+            out[i] = [masks[r:r + k], d[r:r + k]]
+            r += k
+    return out
+
+
+def _empty(hw, device_u8, dev):
+    h, w = hw
+    m = torch.empty(0, h, w, dtype=torch.uint8, device=dev) if device_u8 else np.zeros((0, h, w), np.float32)
+    return [m, np.zeros((0, 5), np.float32)]
