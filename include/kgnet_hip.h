@@ -300,6 +300,28 @@ int kg_host_match_boxes(const float* pb, int P, const float* gb, int G, int gstr
 int kg_mask_areas(const void* masks, int n, long ld, int* area, void* stream);
 int kg_mask_inter_pairs(const void* a, const void* b, const int* pairs, int npairs, long ld, int* inter, void* stream);
 
+/* ---- bit-mask layout: one mask of H x W pixels as 64-bit words, one bit per pixel.
+ *   - row-major; every image row takes wpr = ceil(W / 64) words;
+ *   - bit b (value 1 << b) of word k of row y is pixel (y, 64 k + b); bits at x >= W are zero;
+ *   - one mask occupies ld_words = round_up(H * wpr, 2) words, so every mask of a 16-byte aligned [n][ld_words] buffer starts 16-byte
+ *     aligned; the padding word is zero.
+ * On a little-endian host np.unpackbits(words.view(np.uint8), bitorder="little") recovers the pixels.  A 512 x 512 mask is 32 KB
+ * (bytes: 256 KB, float32: 1 MB).
+ * kg_mask_bits_ld: ld_words of an H x W mask (host helper; -1 on bad arguments).
+ * kg_mask_pack_bits: device masks [n][H][W], float32 (src_is_f32 != 0) or bytes, any non-zero value foreground -> words [n][ld_words].
+ * kg_mask_unpack_bits: words -> device [n][H][W] of 0 / 1, bytes (out_is_u8 != 0) or float32.
+ * kg_bitmask_areas / kg_bitmask_inter_pairs: kg_mask_areas / kg_mask_inter_pairs on words (16-byte loads + popcount, exact int32 counts);
+ * a and b hold na and nb rows -- the masks of all images of a batch that share one size, concatenated -- and a pair that names a row
+ * outside them is not read: its count is -1.
+ * Every entry checks its arguments (null pointers, counts and sizes <= 0, an ld_words that is odd or below kg_mask_bits_ld(H, W)) before
+ * any HIP call. ---- */
+long kg_mask_bits_ld(int H, int W);
+int kg_mask_pack_bits(const void* masks, int src_is_f32, int n, int H, int W, void* words, long ld_words, void* stream);
+int kg_mask_unpack_bits(const void* words, long ld_words, int n, int H, int W, void* out, int out_is_u8, void* stream);
+int kg_bitmask_areas(const void* words, int n, long ld_words, int* area, void* stream);
+int kg_bitmask_inter_pairs(const void* a, int na, const void* b, int nb, const int* pairs, int npairs, long ld_words, int* inter,
+                           void* stream);
+
 /* ---- per-box segmentation branch (KGnet.py:246-267, 321-350): ragged row bookkeeping ---- */
 int kg_seg_build_rows(const int* boxtab8, int nb, int* rowdesc, int* row2box, int* srcrow, void* stream);
 int kg_seg_build_rows_levels(int nlev, const int* const* boxtab8, const int* nb, int* const* rowdesc, int* const* row2box, int* const* srcrow,
@@ -339,6 +361,10 @@ int kg_crop_grad_reduce(const void* ga, int lda, const void* gb, int ldb, long r
  * is OpenCV's published generic INTER_LINEAR float path (oracle/paste.py) ---- */
 int kg_mask_paste(const float* flat, const int* dets, int nd, int input_h, int input_w, int image_h, int image_w,
                   float seg_thresh, void* out, int out_is_u8, void* stream);
+/* the same masks in the bit-mask layout above: words = device [nd][ld_words], bit-identical to kg_mask_paste's thresholded pixels
+ * (same per-pixel expression; a 64-pixel word that cannot reach the detection's box is stored without evaluating it) */
+int kg_mask_paste_bits(const float* flat, const int* dets, int nd, int input_h, int input_w, int image_h, int image_w,
+                       float seg_thresh, void* words, long ld_words, void* stream);
 
 /* ---- gradient scale of the half-precision backward pass (csrc/gradscale.hip) ----
  * kg_grad_scale: out[0] = S = 2^(target_log2 - e), out[1] = 1 / S, where max |v| over the n <= 24 fp32 device tensors

@@ -89,6 +89,11 @@ _SIGS = {
     "kg_host_bin_csr": [P, c_int, c_int, c_int, c_int, c_int, P, P, c_int],               #  call them through load(), not call())
     "kg_mask_areas": [P, c_int, c_long, P, P],
     "kg_mask_inter_pairs": [P, P, P, c_int, c_long, P, P],
+    "kg_mask_bits_ld": [c_int, c_int],
+    "kg_mask_pack_bits": [P, c_int, c_int, c_int, c_int, P, c_long, P],
+    "kg_mask_unpack_bits": [P, c_long, c_int, c_int, c_int, P, c_int, P],
+    "kg_bitmask_areas": [P, c_int, c_long, P, P],
+    "kg_bitmask_inter_pairs": [P, c_int, P, c_int, P, c_int, c_long, P, P],
     "kg_f64_probe": [P, P, P, c_int, P],
     "kg_seg_build_rows": [P, c_int, P, P, P, P],
     "kg_seg_build_rows_levels": [c_int, P, P, P, P, P, P],
@@ -100,9 +105,11 @@ _SIGS = {
     "kg_planes_to_f32": [P, c_int, P, c_int, c_long, c_int, P, P],
     "kg_f32_to_planes": [P, c_int, P, c_int, P, c_int, c_long, c_int, P, P],
     "kg_mask_paste": [P, P, c_int, c_int, c_int, c_int, c_int, c_float, P, c_int, P],
+    "kg_mask_paste_bits": [P, P, c_int, c_int, c_int, c_int, c_int, c_float, P, c_long, P],
     "kg_crop_grad_reduce": [P, c_int, P, c_int, c_long, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P],
 }
-_RESTYPE = {"kg_postproc_workspace_bytes": c_long, "kg_postproc_batch_workspace_bytes": c_long, "kg_nms_batch_workspace_bytes": c_long}
+_RESTYPE = {"kg_postproc_workspace_bytes": c_long, "kg_postproc_batch_workspace_bytes": c_long, "kg_nms_batch_workspace_bytes": c_long,
+            "kg_mask_bits_ld": c_long}
 SYMBOLS = tuple(_SIGS) + ("kg_last_error", "kg_last_kernel")
 
 _lib = None

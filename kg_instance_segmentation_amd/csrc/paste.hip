@@ -100,6 +100,159 @@ extern "C" int kg_mask_paste(const float* flat, const int* dets, int nd, int inp
     return KG_OK;
 }
 
+// ---- bit-packed masks (include/kgnet_hip.h "bit-mask layout") ---------------------------------------------------------------------
+// One mask = ld_words 64-bit words: row y takes wpr = ceil(W / 64) words, bit b of word k of row y is pixel (y, 64 k + b), bits at
+// x >= W and the words from H * wpr on are zero.  A wave owns words: lane b evaluates pixel 64 k + b, __ballot forms the word, lane 0
+// stores it (a vector store).  Every block is 4 waves, every wave walks KG_BITS_WPW consecutive words of one mask.
+#define KG_BITS_WPW 8
+__host__ __device__ static inline long kg_bits_ld(int H, int W) {
+    const long nw = (long)H * ((W + 63) / 64);
+    return (nw + 1) & ~1L;
+}
+static inline bool kg_bits_ld_ok(int H, int W, long ld_words) { return ld_words >= kg_bits_ld(H, W) && ld_words % 2 == 0 && ld_words <= 0x7fffffffL; }
+static inline dim3 kg_bits_grid(int n, long ld_words) {
+    return dim3((unsigned)((ld_words + 4 * KG_BITS_WPW - 1) / (4 * KG_BITS_WPW)), (unsigned)(n < 65535 ? n : 65535));
+}
+
+// kg_mask_paste with the thresholded pixels written as bits.  Per pixel the expression is paste_kernel's own (lin_taps / pasted /
+// resized_patch above, same -ffp-contract=off translation unit).  A word whose 64-pixel span cannot reach the box skips the taps: the
+// source taps s0 / s1 of lin_taps never decrease with the destination index, so paste_kernel's rejection test on the span's two ends
+// (tx.s1 of the last pixel < x1, or tx.s0 of the first >= x2; the row test is the pixel's own) holds for every pixel between them.
+// Such a pixel's value is 0, which is still compared with the threshold (seg_thresh <= 0 makes it foreground, as in paste_kernel).
+__global__ __launch_bounds__(256) void paste_bits_kernel(const float* __restrict__ flat, const PasteDet* __restrict__ dets, int nd, int in_h, int in_w,
+                                                         int out_h, int out_w, float thresh, unsigned long long* __restrict__ words, long ld_words) {
+    const int lane = threadIdx.x & 63, wpr = (out_w + 63) >> 6;
+    const long nw = (long)out_h * wpr;
+    const long r0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * KG_BITS_WPW;
+    const bool same = in_h == out_h && in_w == out_w;
+    for (int k = blockIdx.y; k < nd; k += gridDim.y) {
+        const PasteDet d = dets[k];
+        const float* p = flat + d.off;
+        const bool empty = d.y2 <= d.y1 || d.x2 <= d.x1;
+        int oy = (int)(r0 / wpr), kw = (int)(r0 - (long)oy * wpr), ty_row = -1;
+        Taps ty = {};
+        bool row_skip = true;
+        for (long r = r0; r < r0 + KG_BITS_WPW && r < ld_words; ++r) {
+            unsigned long long word = 0;
+            if (r < nw) {
+                const int xa = kw << 6, xb = xa + 63 < out_w ? xa + 63 : out_w - 1, ox = xa + lane;
+                float v = 0.f;
+                if (empty) {
+                } else if (same) {
+                    if (!(oy < d.y1 || oy >= d.y2 || xb < d.x1 || xa >= d.x2) && ox < out_w) v = pasted(p, d, oy, ox);
+                } else {
+                    if (ty_row != oy) {
+                        ty = lin_taps(oy, in_h, out_h, false);
+                        row_skip = ty.s1 < d.y1 || ty.s0 >= d.y2;
+                        ty_row = oy;
+                    }
+                    bool skip = row_skip;
+                    if (!skip) skip = lin_taps(xb, in_w, out_w, true).s1 < d.x1 || lin_taps(xa, in_w, out_w, true).s0 >= d.x2;
+                    if (!skip && ox < out_w) {
+                        const Taps tx = lin_taps(ox, in_w, out_w, true);
+                        if (!(tx.s1 < d.x1 || tx.s0 >= d.x2)) {
+                            const float r0v = lin_row(pasted(p, d, ty.s0, tx.s0), pasted(p, d, ty.s0, tx.s1), tx);
+                            const float r1v = lin_row(pasted(p, d, ty.s1, tx.s0), pasted(p, d, ty.s1, tx.s1), tx);
+                            const float a = r0v * ty.c0, b = r1v * ty.c1;
+                            v = a + b;
+                        }
+                    }
+                }
+                word = __ballot(ox < out_w && v >= thresh);
+                if (++kw == wpr) { kw = 0; ++oy; }
+            }
+            if (lane == 0) words[(long)k * ld_words + r] = word;
+        }
+    }
+}
+
+// words: device 64-bit words [nd][ld_words], ld_words even and >= kg_mask_bits_ld(image_h, image_w); the other arguments as kg_mask_paste
+extern "C" int kg_mask_paste_bits(const float* flat, const int* dets, int nd, int input_h, int input_w, int image_h, int image_w,
+                                  float seg_thresh, void* words, long ld_words, void* stream) {
+    KG_CHECK_ARG(flat && dets && words, "kg_mask_paste_bits: null pointer");
+    KG_CHECK_ARG(nd >= 0 && input_h > 0 && input_w > 0 && image_h > 0 && image_w > 0, "kg_mask_paste_bits: bad size");
+    KG_CHECK_ARG(kg_bits_ld_ok(image_h, image_w, ld_words), "kg_mask_paste_bits: ld_words %ld too small or odd (need %ld)", ld_words,
+                 kg_bits_ld(image_h, image_w));
+    if (nd == 0) return KG_OK;
+    hipLaunchKernelGGL(paste_bits_kernel, kg_bits_grid(nd, ld_words), dim3(256), 0, (hipStream_t)stream, flat, (const PasteDet*)dets, nd, input_h,
+                       input_w, image_h, image_w, seg_thresh, (unsigned long long*)words, ld_words);
+    KG_CHECK_LAUNCH("mask_paste_bits");
+    return KG_OK;
+}
+
+// dense [n][H][W] (bytes or float32, any non-zero value = foreground) -> words
+template <typename IN>
+__global__ __launch_bounds__(256) void pack_bits_kernel(const IN* __restrict__ m, int n, int H, int W, unsigned long long* __restrict__ words,
+                                                        long ld_words) {
+    const int lane = threadIdx.x & 63, wpr = (W + 63) >> 6;
+    const long nw = (long)H * wpr;
+    const long r0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * KG_BITS_WPW;
+    for (int k = blockIdx.y; k < n; k += gridDim.y) {
+        const IN* src = m + (long)k * H * W;
+        for (long r = r0; r < r0 + KG_BITS_WPW && r < ld_words; ++r) {
+            unsigned long long word = 0;
+            if (r < nw) {
+                const int y = (int)(r / wpr), x = ((int)(r - (long)y * wpr) << 6) + lane;
+                word = __ballot(x < W && src[(long)y * W + x] != (IN)0);
+            }
+            if (lane == 0) words[(long)k * ld_words + r] = word;
+        }
+    }
+}
+// words -> dense [n][H][W] of 0 / 1 (bytes or float32)
+template <typename OUT>
+__global__ __launch_bounds__(256) void unpack_bits_kernel(const unsigned long long* __restrict__ words, long ld_words, int n, int H, int W,
+                                                          OUT* __restrict__ out) {
+    const int lane = threadIdx.x & 63, wpr = (W + 63) >> 6;
+    const long nw = (long)H * wpr;
+    const long r0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * KG_BITS_WPW;
+    for (int k = blockIdx.y; k < n; k += gridDim.y) {
+        OUT* dst = out + (long)k * H * W;
+        for (long r = r0; r < r0 + KG_BITS_WPW && r < nw; ++r) {
+            const int y = (int)(r / wpr), x = ((int)(r - (long)y * wpr) << 6) + lane;
+            const unsigned long long word = words[(long)k * ld_words + r];
+            if (x < W) dst[(long)y * W + x] = (OUT)((word >> lane) & 1ull);
+        }
+    }
+}
+
+// ld_words of an H x W mask (host helper); -1 on bad arguments
+extern "C" long kg_mask_bits_ld(int H, int W) {
+    if (H <= 0 || W <= 0) {
+        kg_set_error("kg_mask_bits_ld: bad size %d x %d", H, W);
+        return -1;
+    }
+    return kg_bits_ld(H, W);
+}
+// masks: device [n][H][W], float32 (src_is_f32 != 0) or bytes; words: device [n][ld_words]
+extern "C" int kg_mask_pack_bits(const void* masks, int src_is_f32, int n, int H, int W, void* words, long ld_words, void* stream) {
+    KG_CHECK_ARG(masks && words, "kg_mask_pack_bits: null pointer");
+    KG_CHECK_ARG(n > 0 && H > 0 && W > 0, "kg_mask_pack_bits: bad size");
+    KG_CHECK_ARG(kg_bits_ld_ok(H, W, ld_words), "kg_mask_pack_bits: ld_words %ld too small or odd (need %ld)", ld_words, kg_bits_ld(H, W));
+    if (src_is_f32)
+        hipLaunchKernelGGL(pack_bits_kernel<float>, kg_bits_grid(n, ld_words), dim3(256), 0, (hipStream_t)stream, (const float*)masks, n, H, W,
+                           (unsigned long long*)words, ld_words);
+    else
+        hipLaunchKernelGGL(pack_bits_kernel<unsigned char>, kg_bits_grid(n, ld_words), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)masks,
+                           n, H, W, (unsigned long long*)words, ld_words);
+    KG_CHECK_LAUNCH("mask_pack_bits");
+    return KG_OK;
+}
+// out: device [n][H][W] of 0 / 1, bytes (out_is_u8 != 0) or float32
+extern "C" int kg_mask_unpack_bits(const void* words, long ld_words, int n, int H, int W, void* out, int out_is_u8, void* stream) {
+    KG_CHECK_ARG(words && out, "kg_mask_unpack_bits: null pointer");
+    KG_CHECK_ARG(n > 0 && H > 0 && W > 0, "kg_mask_unpack_bits: bad size");
+    KG_CHECK_ARG(kg_bits_ld_ok(H, W, ld_words), "kg_mask_unpack_bits: ld_words %ld too small or odd (need %ld)", ld_words, kg_bits_ld(H, W));
+    if (out_is_u8)
+        hipLaunchKernelGGL(unpack_bits_kernel<unsigned char>, kg_bits_grid(n, ld_words), dim3(256), 0, (hipStream_t)stream,
+                           (const unsigned long long*)words, ld_words, n, H, W, (unsigned char*)out);
+    else
+        hipLaunchKernelGGL(unpack_bits_kernel<float>, kg_bits_grid(n, ld_words), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)words,
+                           ld_words, n, H, W, (float*)out);
+    KG_CHECK_LAUNCH("mask_unpack_bits");
+    return KG_OK;
+}
+
 // ---- SEG_loss target preparation on the device (second half: seg_loss.py:57-80) ---------------------------------------
 // For callers whose ground-truth masks are device-resident (float32 [n_i][H][W] tensors on the GPU): the crop of the matched mask
 // [y1:y2, x1:x2] nearest-resized to the predicted patch (h1, w1) -- cv2.resize(..., INTER_NEAREST) as restated by kg_host_crop_masks:

@@ -33,15 +33,58 @@ def _areas(t, ld):
     return out
 
 
+def bit_counts(a, b, pairs):
+    """Exact counts on two bitmasks.BitMasks of one size and one device: (areas of a, areas of b, intersections of the row pairs [P,2]) as
+    device int32 tensors -- one kg_bitmask_areas launch per side and one kg_bitmask_inter_pairs launch, nothing copied to the host."""
+    if (a.h, a.w) != (b.h, b.w):
+        raise _lib.KGLibraryError("detection and ground-truth masks must have the same size")
+    dev = a.words.device
+    wa, wb = a.words.contiguous(), b.words.contiguous()
+    ld = wa.shape[1]
+    pairs = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+    if len(pairs) and (pairs.min() < 0 or pairs[:, 0].max() >= len(a) or pairs[:, 1].max() >= len(b)):
+        raise _lib.KGLibraryError("mask pair index out of range")
+    aa = torch.empty(len(a), dtype=torch.int32, device=dev)
+    ab = torch.empty(len(b), dtype=torch.int32, device=dev)
+    inter = torch.empty(len(pairs), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        if len(a):
+            _lib.call("kg_bitmask_areas", ptr(wa), len(a), c_long(ld), ptr(aa), stream_ptr())
+        if len(b):
+            _lib.call("kg_bitmask_areas", ptr(wb), len(b), c_long(ld), ptr(ab), stream_ptr())
+        if len(pairs):
+            _lib.call("kg_bitmask_inter_pairs", ptr(wa), len(a), ptr(wb), len(b), ptr(ops.h2d(pairs, dev)), len(pairs), c_long(ld), ptr(inter),
+                      stream_ptr())
+    return aa, ab, inter
+
+
+def iou_from_counts(aa, ab, ia, pairs):
+    """eval_parts.mask_iou (eval_parts.py:4-9) from integer counts: float64 intersection / union, 0 where the union is empty."""
+    aa, ab, ia = np.asarray(aa, np.int64), np.asarray(ab, np.int64), np.asarray(ia, np.int64)
+    union = aa[pairs[:, 0]] + ab[pairs[:, 1]] - ia
+    out = np.zeros(len(pairs), np.float64)
+    ok = union >= 1
+    out[ok] = ia[ok].astype(np.float64) / union[ok].astype(np.float64)
+    return out
+
+
 def mask_iou_table(det_masks, gt_masks, pairs, device=None):
     """IoU (eval_parts.mask_iou semantics: 0 if the union is empty) of the (detection, GT) index pairs [P,2].
-    Returns a float64 array [P]."""
+    Returns a float64 array [P].  Either side may be a bitmasks.BitMasks: the counts then run on bits (a dense side is packed first)."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     if dev.type != "cuda":
         raise _lib.KGLibraryError("eval_parts (MI355X build) needs a GPU device")
     pairs = np.asarray(pairs, np.int32).reshape(-1, 2)
     if len(pairs) == 0:
         return np.zeros(0, np.float64)
+    from .bitmasks import BitMasks
+    if isinstance(det_masks, BitMasks) or isinstance(gt_masks, BitMasks):
+        if device is None:
+            dev = (det_masks if isinstance(det_masks, BitMasks) else gt_masks).device
+        a, b = BitMasks.from_dense(det_masks, dev), BitMasks.from_dense(gt_masks, dev)
+        aa, ab, inter = bit_counts(a, b, pairs)
+        c = torch.cat([aa, ab, inter]).cpu().numpy()
+        return iou_from_counts(c[:len(a)], c[len(a):len(a) + len(b)], c[len(a) + len(b):], pairs)
     with torch.cuda.device(dev):
         a, ld = _device_masks(det_masks, dev)
         b, ld2 = _device_masks(gt_masks, dev)

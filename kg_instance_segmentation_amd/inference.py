@@ -28,25 +28,29 @@ def size_groups(image_sizes):
     return list(groups.items())
 
 
-def predict(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None, device_u8=False, max_workspace_bytes=None):
+def predict(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None, device_u8=False, max_workspace_bytes=None, packed=False):
     """test_inference + post_processing (test.py:88-157) for the batch x [N,3,H,W] (already resized and normalised as test.py:91-92 does).
     The model's mode is left as it is.  image_sizes: (h, w) of every source image (default: the input size).
     Returns N entries: None (no detection) or [masks float32 [n, h, w] in {0, 1}, dets float32 [n, 5] (y1, x1, y2, x2, conf) in image pixels],
-    the masks as uint8 device tensors with device_u8=True."""
+    the masks as uint8 device tensors with device_u8=True, as a bitmasks.BitMasks (device words, one bit per pixel) with packed=True."""
     with torch.no_grad():
         d0, d1, d2, d3, feat_seg = model.forward_dec(x)
     return predict_from_heads(model, [d0, d1, d2, d3], feat_seg, x.shape[2], x.shape[3], nms_thresh, seg_thresh, image_sizes, device_u8,
-                              max_workspace_bytes)
+                              max_workspace_bytes, packed)
 
 
 def predict_from_heads(model, dec, feat_seg, input_h, input_w, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None, device_u8=False,
-                       max_workspace_bytes=None):
-    """The part of predict() after forward_dec: dec = ([kp, short, mid] x 4) and feat_seg of a batch, as forward_dec returns them."""
+                       max_workspace_bytes=None, packed=False, dets=None):
+    """The part of predict() after forward_dec: dec = ([kp, short, mid] x 4) and feat_seg of a batch, as forward_dec returns them.
+    dets: what postprocessing.detect_batch(dec, nms_thresh) returned, for a caller that already ran it (evaluation.evaluate)."""
     N = dec[0][0].shape[0]
     sizes = [(int(input_h), int(input_w))] * N if image_sizes is None else [(int(h), int(w)) for h, w in image_sizes]
     if len(sizes) != N:
         raise _lib.KGLibraryError(f"predict: {len(sizes)} image sizes for {N} images")
-    dets = postprocessing.detect_batch(dec, nms_thresh, max_workspace_bytes=max_workspace_bytes)
+    if dets is None:
+        dets = postprocessing.detect_batch(dec, nms_thresh, max_workspace_bytes=max_workspace_bytes)
+    elif len(dets) != N:
+        raise _lib.KGLibraryError(f"predict: {len(dets)} detection entries for {N} images")
     if all(d is None for d in dets):
         return [None] * N
     boxes = [d if d is not None else np.zeros((0, 5), np.float64) for d in dets]   # (one array per image, as test.py:119 passes [bboxes])
@@ -57,7 +61,7 @@ def predict_from_heads(model, dec, feat_seg, input_h, input_w, nms_thresh=0.5, s
     if meta is None:                     # every box fell outside the feature maps: no mask rows at all
         for i in range(N):
             if dets[i] is not None:
-                out[i] = _empty(sizes[i], device_u8, feat_seg[0].device)
+                out[i] = _empty(sizes[i], device_u8, feat_seg[0].device, packed)
         return out
     rng = image_row_ranges(meta["img"], N)
     off, hh, ww, bx = np.asarray(meta["off"]), np.asarray(meta["h"]), np.asarray(meta["w"]), np.asarray(meta["boxes"])
@@ -66,7 +70,8 @@ def predict_from_heads(model, dec, feat_seg, input_h, input_w, nms_thresh=0.5, s
         if not imgs:
             continue
         sel = np.concatenate([np.arange(*rng[i]) for i in imgs]).astype(np.int64)
-        masks, d = postprocessing.paste_rows(meta["flat"], off[sel], hh[sel], ww[sel], bx[sel], input_h, input_w, w, h, seg_thresh, device_u8)
+        masks, d = postprocessing.paste_rows(meta["flat"], off[sel], hh[sel], ww[sel], bx[sel], input_h, input_w, w, h, seg_thresh, device_u8,
+                                              packed)
         r = 0
         for i in imgs:
             k = rng[i][1] - rng[i][0]
@@ -75,7 +80,10 @@ def predict_from_heads(model, dec, feat_seg, input_h, input_w, nms_thresh=0.5, s
     return out
 
 
-def _empty(hw, device_u8, dev):
+def _empty(hw, device_u8, dev, packed=False):
     h, w = hw
+    if packed:
+        from .bitmasks import BitMasks
+        return [BitMasks.empty(h, w, dev), np.zeros((0, 5), np.float32)]
     m = torch.empty(0, h, w, dtype=torch.uint8, device=dev) if device_u8 else np.zeros((0, h, w), np.float32)
     return [m, np.zeros((0, 5), np.float32)]

@@ -285,23 +285,25 @@ def detect_batch(dec, nms_thresh=0.5, max_workspace_bytes=None):
     return [rows[starts[i]:starts[i + 1]].copy() if nk[i] else None for i in range(N)]
 
 
-def paste_masks(predictions, input_h, input_w, image_w, image_h, seg_thresh, device_u8=False):
+def paste_masks(predictions, input_h, input_w, image_w, image_h, seg_thresh, device_u8=False, packed=False):
     """== the reference driver's `post_processing` (test.py:127-157) for the predictions of `model.forward_seg`: every mask patch is
     resized to its (rounded, clamped) box, pasted into an (input_h, input_w) canvas, resized to the image and thresholded -- in one
     kernel launch for all detections (kg_mask_paste) instead of two cv2.resize calls and a full-size host array per detection.
     Returns [masks float32 [n, image_h, image_w] in {0, 1}, dets float32 [n, 5] = (y1, x1, y2, x2, conf) in image pixels] like the
-    reference, or None; device_u8=True keeps the masks on the GPU as bytes (what eval_parts.seg_evaluation consumes)."""
+    reference, or None; device_u8=True keeps the masks on the GPU as bytes (what eval_parts.seg_evaluation consumes), packed=True as a
+    bitmasks.BitMasks (one bit per pixel, kg_mask_paste_bits: the same pixels in 1/8 of the bytes)."""
     if predictions is None:
         return None
     meta = getattr(predictions, "kg_meta", None)
     if meta is None:
         raise _lib.KGLibraryError("paste_masks needs the predictions object returned by this package's forward_seg")
-    return paste_rows(meta["flat"], meta["off"], meta["h"], meta["w"], meta["boxes"], input_h, input_w, image_w, image_h, seg_thresh, device_u8)
+    return paste_rows(meta["flat"], meta["off"], meta["h"], meta["w"], meta["boxes"], input_h, input_w, image_w, image_h, seg_thresh, device_u8,
+                      packed)
 
 
-def paste_rows(flat, off, h, w, boxes, input_h, input_w, image_w, image_h, seg_thresh, device_u8=False):
+def paste_rows(flat, off, h, w, boxes, input_h, input_w, image_w, image_h, seg_thresh, device_u8=False, packed=False):
     """paste_masks over an explicit list of mask rows (patch offsets / sizes in the flat probability buffer and their boxes, as in
-    forward_seg's kg_meta): one kg_mask_paste launch.  Returns [masks, dets] as paste_masks does."""
+    forward_seg's kg_meta): one kg_mask_paste (packed=True: kg_mask_paste_bits) launch.  Returns [masks, dets] as paste_masks does."""
     n = len(off)
     dev = flat.device
     b = np.asarray(boxes, np.float32).reshape(-1, 5)
@@ -311,6 +313,14 @@ def paste_rows(flat, off, h, w, boxes, input_h, input_w, image_w, image_h, seg_t
                     np.zeros(n, np.int64)], 1).astype(np.int32)
     dets = np.stack([y1.astype(np.float64) / input_h * image_h, x1.astype(np.float64) / input_w * image_w,
                      y2.astype(np.float64) / input_h * image_h, x2.astype(np.float64) / input_w * image_w, b[:, 4].astype(np.float64)], 1).astype(np.float32)
+    if packed:
+        from .bitmasks import BitMasks
+        bm = BitMasks.empty(int(image_h), int(image_w), dev, n)
+        if n:
+            with torch.cuda.device(dev):
+                _lib.call("kg_mask_paste_bits", ptr(flat), ptr(ops.h2d(tab.reshape(-1), dev)), n, int(input_h), int(input_w), int(image_h),
+                          int(image_w), _lib.c_float(float(seg_thresh)), ptr(bm.words), c_long(bm.words.shape[1]), stream_ptr())
+        return [bm, dets]
     out = torch.empty(n, int(image_h), int(image_w), dtype=torch.uint8 if device_u8 else torch.float32, device=dev)
     if n:
         with torch.cuda.device(dev):
