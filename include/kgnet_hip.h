@@ -273,6 +273,30 @@ int kg_nms_batch(int N, const double* boxes, const int* nbox, int box_cap, doubl
  * [55][H][W] (kp 5 | short 10 | mid 40), bit-identical to the reference's float32 tensors ---- */
 int kg_gt_maps(const float* kps, int n, int H, int W, float* out, void* stream);
 
+/* ---- training samples prepared on the device (BaseDataset.__getitem__, dataset_base.py:81-116, under train.py:77-85's transform
+ * pipelines; csrc/sampleprep.hip).  imgs = device table of N 80-byte records, one per image:
+ *   { const uint8* img [h][w][3]; const void* masks; int h, w, He, We; int oy, ox, flags, perm; float delta, alpha; int inst0, n;
+ *     long ld; long pad; }
+ * masks = bytes [n][h][w] (any non-zero value foreground) or, with flag 4, 64-bit words [n][ld] in the bit-mask layout below; (He, We) =
+ * canvas after Expand and (oy, ox) the paste window's origin (transforms.py:86-106; source size and 0 when off); flags 1 / 2 = mirror
+ * along w / h (transforms.py:148-162); perm = source channel of output channel c in bits 2c..2c+1 (transforms.py:56-66); delta, alpha =
+ * brightness, contrast (transforms.py:22-46; 0 and 1 when off); inst0 = first instance of the image in the batch-wide instance order;
+ * ld = elements between two masks.  H, W = network input size, multiples of 8, W <= 4096.
+ * kg_sp_image: out = device float32 [N][3][H][W]: float32 INTER_LINEAR resize of the photometric, expanded, mirrored image
+ *   (transforms.py:165-170; the rule of kg_mask_paste), then clip, / 255 - 0.5, CHW (dataset_base.py:104-106).  One launch.
+ * kg_sp_warp_masks: out = device bytes [ntot][H][W] of 0 / 1, the nearest resize of the expanded, mirrored masks (transforms.py:171-176:
+ *   src = min(floor(dst * scale), size - 1), scale = 1 / (dsize / ssize) in double) of all instances of the batch, inst_img = device
+ *   int32 [ntot], the image of every instance; box = device int32 [ntot][16], zero-filled by the caller, receives the bounding boxes of
+ *   the ones at divide scales 1, 2, 4, 8 (dataset_base.py:58-71), encoded as maxima.  One launch; the expanded canvas never exists.
+ * kg_sp_boxes: box -> per image, in instance order: kp = device float32 [4][ntot][5][2], the keypoints (x, y) of tl, tr, bl, br, centre
+ *   of the instances kept at each scale (dataset_base.py:72-78); gtb = device float32 [ntot][5] = (y1, x1, y2, x2, 1) and keep = device
+ *   int32 [ntot] (instance index) of the instances load_gt_masks_bboxes keeps (dataset_base.py:43-56); the lists of image i start at row
+ *   inst0 of their table; counts = device int32 [N][5] (scales 1, 2, 4, 8, gt). ---- */
+int kg_sp_image(const void* imgs, int N, int H, int W, float* out, void* stream);
+int kg_sp_warp_masks(const void* imgs, const int* inst_img, int ntot, int H, int W, void* out, int* box, void* stream);
+int kg_sp_boxes(const void* imgs, int N, const int* box, int ntot, int kp_radius, int* counts, float* gtb, float* kp, int* keep,
+                void* stream);
+
 /* ---- fused multi-tensor Adam step (train.py:71,154), fp32, torch.optim.Adam's operation order.  jobs = device array of 48-byte
  * records {float* p; const float* g; float* m; float* v; long n; int blk0; int pad;}, blk0 = first workgroup of the job (4096
  * elements per workgroup); step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t) ---- */

@@ -81,6 +81,9 @@ _SIGS = {
     "kg_nms_batch_workspace_bytes": [c_int, c_int],
     "kg_nms_batch": [c_int, P, P, c_int, c_double, P, c_long, P, P, P],
     "kg_gt_maps": [P, c_int, c_int, c_int, P, P],
+    "kg_sp_image": [P, c_int, c_int, c_int, P, P],
+    "kg_sp_warp_masks": [P, P, c_int, c_int, c_int, P, P, P],
+    "kg_sp_boxes": [P, c_int, P, c_int, c_int, P, P, P, P, P],
     "kg_adam_step": [P, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float, P],
     "kg_host_crop_masks": [P, P, c_int, c_int, c_int, P],
     "kg_crop_masks": [P, P, c_int, c_int, c_int, P, P],

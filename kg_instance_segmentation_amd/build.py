@@ -36,6 +36,7 @@ SOURCES = {
     "optim.hip": ["-ffp-contract=off"],
     "seg.hip": [],
     "paste.hip": ["-ffp-contract=off"],
+    "sampleprep.hip": ["-ffp-contract=off"],
     "gradscale.hip": [],
     "conv_tiny.hip": [],
     "conv3_ws.hip": [],
