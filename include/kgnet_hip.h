@@ -193,6 +193,15 @@ int kg_bn_bwd(const void* x, int ldx, const void* dy, int lddy, const float* gam
               const float* invstd, float* dgamma, float* dbeta, int accumulate, void* dx, int lddx, int M, int C,
               float* scratch, int scratch_floats, const float* parts, int nb_parts, const float* parts_scale,
               const kg_planes_t* planes, void* stream);
+/* Backward of a FROZEN BatchNorm2d (running statistics as constants in a training step -- torchvision's FrozenBatchNorm2d; the reference
+ * fine-tunes an ImageNet backbone at batch size 2, train.py:22,71): y = x * scale + shift, scale = gamma * rsqrt(running_var + eps)
+ * (kg_bn_scale_shift_eval).  ONE streaming pass: dx = scale[c] * dy, dbeta[c] = sum dy, dgamma[c] = sum dy * (x - running_mean[c]) *
+ * rsqrt(running_var[c] + eps) (block partials in scratch, combined in double in fixed order: reproducible, no atomics).
+ * dgamma == dbeta == NULL (gamma / beta frozen too): dx = scale[c] * dy alone -- x, running_mean, running_var, scratch may be NULL.
+ * planes: a = x, b = dy, y = dx. */
+int kg_bn_bwd_frozen(const void* x, int ldx, const void* dy, int lddy, const float* scale, const float* running_mean,
+                     const float* running_var, float eps, float* dgamma, float* dbeta, int accumulate, void* dx, int lddx,
+                     int M, int C, float* scratch, int scratch_floats, const kg_planes_t* planes, void* stream);
 /* BACKWARD statistics from the input gradient that completes dy (train-mode BatchNorm under autograd, KGnet.py:82-93 + train.py:153):
  * kg_conv_bstats_begin arms the calling host thread's next dense input-gradient launch (kg_conv2d_igemm mode 1 on the gather kernel, kg_conv2d_halo
  * with flip = 1 and KS = 3; output channels a multiple of 64): besides storing the gradient rows g (after the residual add and the ReLU mask of

@@ -22,6 +22,9 @@ RANGE of the half policies (nothing is clamped; a violation surfaces as inf / Na
 |x| <= 65504; a non-finite parameter gradient raises the sticky flag grad_overflowed().  Use "fp32bf" for weights outside that range.
 Head maps and the feature maps c0..c4 are returned as fp32 tensors like the reference's (KGnet.py:318;
 the feature maps are NCHW-shaped with channels-last memory).
+Fine-tuning (an extension; the reference's optimizer already filters on requires_grad, train.py:71): model.freeze_bn() puts BatchNorm layers on
+their running statistics in the forward and the backward pass whatever `training` is, and requires_grad=False on a parameter is honoured by
+the backward pass (no weight gradient; nothing at all below the deepest trainable layer).
 """
 import math
 import os
@@ -180,6 +183,9 @@ class ResNet(nn.Module):
         self.layers_tab = arch.layers_table(layers)          # KGnet.py:135-137 builds layers[0..2] only
         self._slot_cache = {}            # get_tensor: key -> (the node's _parameters dict, its _buffers dict, leaf name)
         self._param_keys = []
+        self._bn_prefixes = []           # the BatchNorm layers ("bn1", "layer2.0.bn3", ...: 43 for resnet50), forward order
+        self._frozen_bn = frozenset()    # prefixes of the layers that normalise with their running statistics whatever `training` is (freeze_bn)
+        self._bn_affine_cleared = set()  # BatchNorm weight / bias keys whose requires_grad freeze_bn cleared (freeze_bn(False) restores exactly those)
         for key, shape, kind in arch.state_spec(layers):
             parts = key.split(".")
             node = self
@@ -203,6 +209,7 @@ class ResNet(nn.Module):
                 node.register_parameter(parts[-1], nn.Parameter(torch.zeros(shape)))
             elif kind == "bn_rm":
                 node.register_buffer(parts[-1], torch.zeros(shape))
+                self._bn_prefixes.append(key.rsplit(".", 1)[0])
             elif kind == "bn_rv":
                 node.register_buffer(parts[-1], torch.ones(shape))
             else:
@@ -226,6 +233,41 @@ class ResNet(nn.Module):
         """one of engine.PRECISIONS ("fp32" = default) -- see the module docstring."""
         self._engine.set_precision(precision)
         self._seg.invalidate_caches()
+        return self
+
+    @property
+    def frozen_bn(self):
+        """prefixes of the frozen BatchNorm layers (freeze_bn); not part of state_dict()"""
+        return self._frozen_bn
+
+    def freeze_bn(self, mode=True, affine=True, layers=None):
+        """Fine-tuning with frozen BatchNorm (torchvision's FrozenBatchNorm2d; the reference trains an ImageNet backbone at batch size 2,
+        train.py:22,71).  A frozen layer normalises with running_mean / running_var in the forward AND the backward pass whatever
+        `model.training` is, and never writes its running statistics or num_batches_tracked.  layers: BatchNorm key prefixes ("bn1",
+        "layer2.0.bn3", ...; default: all of them).  affine=True also clears requires_grad of the layers' weight and bias (conv -> BatchNorm
+        then runs as one launch in the recorded forward as well); freeze_bn(False) puts the layers back into train-mode behaviour and
+        restores requires_grad where freeze_bn had cleared it.  train() / eval() are unchanged.  Returns self."""
+        known = set(self._bn_prefixes)
+        sel = list(self._bn_prefixes) if layers is None else [str(p) for p in ([layers] if isinstance(layers, str) else layers)]
+        bad = [p for p in sel if p not in known]
+        if bad:
+            raise ValueError(f"freeze_bn: unknown BatchNorm layer(s) {bad}; the layers are {self._bn_prefixes[:3]} ... {self._bn_prefixes[-1]!r}")
+        if mode:
+            self._frozen_bn = self._frozen_bn | frozenset(sel)
+            if affine:
+                for p in sel:
+                    for leaf in (".weight", ".bias"):
+                        t = self.get_tensor(p + leaf)
+                        if t.requires_grad:
+                            t.requires_grad_(False)
+                            self._bn_affine_cleared.add(p + leaf)
+        else:
+            self._frozen_bn = self._frozen_bn - frozenset(sel)
+            for p in sel:
+                for leaf in (".weight", ".bias"):
+                    if p + leaf in self._bn_affine_cleared:
+                        self.get_tensor(p + leaf).requires_grad_(True)
+                        self._bn_affine_cleared.discard(p + leaf)
         return self
 
     def grad_overflowed(self, reset=True):

@@ -58,6 +58,7 @@ _SIGS = {
     "kg_bn_finalize_train": [P, c_int, c_int, c_int, P, P, P, P, c_float, c_float, P, P, P, P, P],
     "kg_bn_apply": [P, c_int, P, P, P, c_int, P, c_int, c_int, c_int, c_int, P, P],
     "kg_bn_bwd": [P, c_int, P, c_int, P, P, P, P, P, c_int, P, c_int, c_int, c_int, P, c_int, P, c_int, P, P, P],
+    "kg_bn_bwd_frozen": [P, c_int, P, c_int, P, P, P, c_float, P, P, c_int, P, c_int, c_int, c_int, P, c_int, P, P],
     "kg_maxpool3s2_fwd": [P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, P, P],
     "kg_maxpool3s2_bwd": [P, c_int, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, P, P],
     "kg_bilinear_fwd": [P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_long, P, P],

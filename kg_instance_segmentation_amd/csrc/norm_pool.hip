@@ -293,6 +293,110 @@ extern "C" int kg_bn_bwd(const void* x, int ldx, const void* dy, int lddy, const
     return KG_OK;
 }
 
+// Frozen BatchNorm backward (running statistics are constants: y = x * scale + shift with scale = gamma * rsqrt(running_var + eps)):
+//   dx = scale * dy,   dbeta = sum dy,   dgamma = sum dy * (x - running_mean) * rsqrt(running_var + eps)
+// in ONE pass over x and dy: colreduce_kernel's geometry ([32 row lanes][8 chunk lanes], a 64-channel slab and a contiguous row range
+// per workgroup, partials [nb][C][2]) with the dx store riding along; bn_finalize_bwd_kernel combines the partials (double, fixed order).
+__global__ __launch_bounds__(256) void bn_bwd_frozen_stats_kernel(const RowsR x, const RowsR dy, const float* __restrict__ scale,
+                                                                  const float* __restrict__ rmean, const float* __restrict__ rvar, float eps,
+                                                                  const RowsW dx, float* __restrict__ part, int M, int C, int rows_per_block) {
+    __shared__ float red[32][8][16];
+    const int cl = threadIdx.x & 7, rl = threadIdx.x >> 3;
+    const int c0 = blockIdx.y * 64 + cl * 8;
+    float s0[8], s1[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s0[e] = s1[e] = 0.f;
+    if (c0 < C) {
+        float mu[8], is[8], sc[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { mu[e] = rmean[c0 + e]; is[e] = 1.f / sqrtf(rvar[c0 + e] + eps); sc[e] = scale[c0 + e]; }
+        int r0 = blockIdx.x * rows_per_block, r1 = r0 + rows_per_block;
+        if (r1 > M) r1 = M;
+        // two rows per trip: both rows' loads are issued before the first store (the compiler cannot move a load across a store it cannot
+        // prove disjoint), so a thread keeps 2 x (x planes + dy planes) 16-byte loads in flight
+        for (int r = r0 + rl; r < r1; r += 64) {
+            const bool two = r + 32 < r1;
+            float xa[8], da[8], xb[8], db[8], v[8];
+            rd8(x, r, c0, xa); rd8(dy, r, c0, da);
+            if (two) { rd8(x, r + 32, c0, xb); rd8(dy, r + 32, c0, db); }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float d = da[e];
+                s0[e] += d; s1[e] += d * ((xa[e] - mu[e]) * is[e]);
+                v[e] = sc[e] * d;
+            }
+            wr8(dx, r, c0, v);
+            if (two) {
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float d = db[e];
+                    s0[e] += d; s1[e] += d * ((xb[e] - mu[e]) * is[e]);
+                    v[e] = sc[e] * d;
+                }
+                wr8(dx, r + 32, c0, v);
+            }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { red[rl][cl][e] = s0[e]; red[rl][cl][8 + e] = s1[e]; }
+    __syncthreads();
+    if (threadIdx.x < 128) {
+        const int c = threadIdx.x & 63, q = threadIdx.x >> 6;  // q: which sum
+        float t = 0.f;
+        for (int k = 0; k < 32; ++k) t += red[k][c >> 3][q * 8 + (c & 7)];
+        const int cg = blockIdx.y * 64 + c;
+        if (cg < C) part[((long)blockIdx.x * C + cg) * 2 + q] = t;
+    }
+}
+// dx = scale * dy alone (gamma and beta frozen too: x is never read)
+__global__ void bn_bwd_frozen_scale_kernel(const RowsR dy, const float* __restrict__ scale, const RowsW dx, long M, int C8) {
+    long total = M * C8;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        long r; int c; kg_divmod(i, C8, &r, &c); c *= 8;
+        float v[8];
+        rd8(dy, r, c, v);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] *= scale[c + e];
+        wr8(dx, r, c, v);
+    }
+}
+// planes: a = x, b = dy, y = dx.  scale: gamma * rsqrt(running_var + eps) (kg_bn_scale_shift_eval).  dgamma == dbeta == NULL: the pure
+// dx = scale * dy stream (x, running_mean, running_var and scratch are not touched and may be NULL); otherwise scratch holds 3 * C floats
+// + the partials [nb][C][2].  No atomics: the same bits run to run.
+extern "C" int kg_bn_bwd_frozen(const void* x, int ldx, const void* dy, int lddy, const float* scale, const float* running_mean,
+                                const float* running_var, float eps, float* dgamma, float* dbeta, int accumulate, void* dx, int lddx,
+                                int M, int C, float* scratch, int scratch_floats, const kg_planes_t* planes, void* stream) {
+    KG_PLANES(planes);
+    KG_CHECK_ARG(dy && scale && dx, "kg_bn_bwd_frozen: null pointer");
+    KG_CHECK_ARG((dgamma != nullptr) == (dbeta != nullptr), "kg_bn_bwd_frozen: dgamma and dbeta come together");
+    KG_CHECK_ARG(M >= 1 && C >= 8 && C % 8 == 0 && lddy % 8 == 0 && lddx % 8 == 0 && lddy >= C && lddx >= C, "kg_bn_bwd_frozen: C/ld must be multiples of 8, ld >= C");
+    const RowsR dyr{(const bf16_t*)dy, lddy, pp.b_planes, pp.b_pstride};
+    const RowsW dxw{(bf16_t*)dx, lddx, pp.y_planes, pp.y_pstride};
+    hipStream_t st = (hipStream_t)stream;
+    if (!dgamma) {
+        long total = (long)M * (C / 8);
+        int blocks = (int)((total + 255) / 256); if (blocks > 16384) blocks = 16384;
+        hipLaunchKernelGGL(bn_bwd_frozen_scale_kernel, dim3(blocks), dim3(256), 0, st, dyr, scale, dxw, (long)M, C / 8);
+        KG_CHECK_LAUNCH("bn_bwd_frozen");
+        return KG_OK;
+    }
+    KG_CHECK_ARG(x && running_mean && running_var && scratch, "kg_bn_bwd_frozen: null pointer");
+    KG_CHECK_ARG(ldx % 8 == 0 && ldx >= C, "kg_bn_bwd_frozen: C/ld must be multiples of 8, ld >= C");
+    int nb, rpb;
+    KG_CHECK_ARG(reduce_geometry(M, C, scratch_floats - 3 * C, &nb, &rpb), "kg_bn_bwd_frozen: scratch too small");
+    // bn_finalize_bwd_kernel serves for its fixed-order double combine of the partials into dgamma / dbeta alone: the train-mode dx coefficients
+    // it also writes go to scratch and are not used, and its gamma / invstd arguments (read only for those coefficients) are dummies -- `scale`
+    // twice, because it is a valid [C] array
+    float* coef = scratch;
+    float* part = scratch + 3 * C;
+    hipLaunchKernelGGL(bn_bwd_frozen_stats_kernel, dim3(nb, (C + 63) / 64), dim3(256), 0, st, RowsR{(const bf16_t*)x, ldx, pp.a_planes, pp.a_pstride},
+                       dyr, scale, running_mean, running_var, eps, dxw, part, M, C, rpb);
+    hipLaunchKernelGGL(bn_finalize_bwd_kernel, dim3(C), dim3(64), 0, st, part, nb, C, (long)M, scale, scale, dgamma, dbeta, accumulate, coef,
+                       (const float*)nullptr);
+    KG_CHECK_LAUNCH("bn_bwd_frozen");
+    return KG_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // MaxPool2d(3, stride 2, pad 1) (KGnet.py:134).  First maximum in (kh,kw) scan order wins ties,
 // as torch's max_pool2d does.

@@ -232,12 +232,21 @@ class Engine:
     def invalidate_caches(self):
         """Forget every packed-weight / folded-BatchNorm copy (call after writing parameters behind PyTorch's back)."""
         self.specs, self.bn_eval, self.fusedT, self.heads2_seen = {}, {}, {}, {}
+        self.bn_gen = {}       # BatchNorm prefix -> count of forwards that ran the layer while something could write it (bn_eval_affine)
         self._heads2 = None
         self.prepack_state = None
 
     # ---- parameters ---------------------------------------------------------------------------
     def P(self, key):
         return self.m.get_tensor(key)
+
+    def bn_batch_stats(self, p):
+        """BatchNorm layer p normalises with the statistics of the batch (and updates its running statistics): the model is in train mode
+        and the layer is not frozen (KGnet.freeze_bn)"""
+        return self.m.training and p not in self.m.frozen_bn
+
+    def trainable(self, keys):
+        return any(self.P(k).requires_grad for k in keys)
 
     def new_grad(self, key, like):
         """Destination of a parameter gradient: a fresh tensor, or -- data parallel -- the parameter's slot in the persistent flat
@@ -374,14 +383,21 @@ class Engine:
             s.pwT.stale = False
 
     # ---- ops ------------------------------------------------------------------------------------
-    def conv(self, xv, s, N, H, W, relu, out=None, y_f32=None, tile=0, oP=None, bn_stats=False, affine=None, res=None):
+    def conv(self, xv, s, N, H, W, relu, out=None, y_f32=None, tile=0, oP=None, bn_stats=False, affine=None, res=None, frozen_bn=False):
         """xv: Var over [N*H*W, >=cin_pad]; returns Var over [N*OH*OW, cout] (or fp32 NCHW when y_f32).
         oP: planes of the output (default: the conv's own precision).  bn_stats: the output feeds a train-mode BatchNorm -- the conv
         kernel also writes the statistics partials of its output when it can (ops.conv_stats_begin); the Var then carries them.
-        affine = (scale, shift) fp32 [cout] / res (Var): inference only (conv_bn) -- y = act(conv * scale + shift + res) in the conv's epilogue."""
+        affine = (scale, shift) fp32 [cout] / res (Var): y = act(conv * scale + shift + res) in the conv's epilogue (conv_bn) -- inference, or
+        a recorded forward through a BatchNorm that is frozen together with its weight and bias (frozen_bn): the backward then multiplies the
+        output's gradient by scale[c] and runs the conv's own gradients on the product."""
         train = self.tape is not None
-        assert not (train and (affine is not None or res is not None))
+        assert not train or frozen_bn or (affine is None and res is None)
         xv.uses += 1
+        if res is not None:
+            res.uses += 1
+        pkeys = [n + ".weight" for n in s.names] + ([n + ".bias" for n in s.names] if s.has_bias else [])
+        wreq = train and self.trainable(pkeys)       # (a conv whose parameters are all frozen computes no weight gradient)
+        req = xv.req or wreq or (res is not None and res.req)
         self.prepare(s, need_T=train and xv.req)
         OH = (H + 2 * s.pad - s.k) // s.stride + 1
         OW = (W + 2 * s.pad - s.k) // s.stride + 1
@@ -404,31 +420,39 @@ class Engine:
         finally:
             if arm:          # (always disarm: an exception in the launch must not leave the side channel armed for the next conv)
                 nb = ops.conv_stats_end(self.fmt)
-        yv = Var(out, s.cout, relu=relu, gP=s.gP)
+        yv = Var(out, s.cout, relu=relu, req=req, gP=s.gP)
         if arm:
             yv.bn_part = (part, nb) if nb > 0 else None
-        if train:
+        if train and req:
             def bwd():
                 g = yv.take_grad()
                 if g is None:
                     return
                 if yv.boundary:
                     self.renormalise(g, yv.C)
+                if affine is not None:       # frozen BatchNorm folded into the forward epilogue: dconv = scale[c] * g (in g's own scale)
+                    gy = g
+                    if wreq or xv.req:
+                        g = ops.alloc_pt(M, s.cout, s.gP, dev, dtype=self.dt)
+                        ops.bn_bwd_frozen(None, gy, s.cout, affine[0], None, None, None, None, g)
+                    if res is not None and res.req:
+                        res.add_grad(gy, masked=False)
                 g = trunc(g, s.gP)       # (an output stored in more planes than this conv computes in: its gradient is rounded alike)
-                grads, off = [], 0
-                for n, co in zip(s.names, s.couts):
-                    w = self.P(n + ".weight")
-                    gw = self.new_grad(n + ".weight", w)
-                    self.param_grads[n + ".weight"] = gw
-                    grads.append((gw, off, co))
-                    off += co
-                db = torch.empty(s.cout, dtype=torch.float32, device=dev) if s.has_bias else None
-                ops.conv_wgrad(trunc(xin, min(s.gP, self.pw)), trunc(g, self.pw), s.cin, s.cout, geom, grads, N=N, bias_out=db)
-                if s.has_bias:
-                    off = 0
+                if wreq:
+                    grads, off = [], 0
                     for n, co in zip(s.names, s.couts):
-                        self.param_grads[n + ".bias"] = self.place_grad(n + ".bias", db[off:off + co])
+                        w = self.P(n + ".weight")
+                        gw = self.new_grad(n + ".weight", w)
+                        self.param_grads[n + ".weight"] = gw
+                        grads.append((gw, off, co))
                         off += co
+                    db = torch.empty(s.cout, dtype=torch.float32, device=dev) if s.has_bias else None
+                    ops.conv_wgrad(trunc(xin, min(s.gP, self.pw)), trunc(g, self.pw), s.cin, s.cout, geom, grads, N=N, bias_out=db)
+                    if s.has_bias:
+                        off = 0
+                        for n, co in zip(s.names, s.couts):
+                            self.param_grads[n + ".bias"] = self.place_grad(n + ".bias", db[off:off + co])
+                            off += co
                 if xv.req:
                     existing = xv.grad if xv.parent is None else None
                     if existing is not None:
@@ -460,7 +484,13 @@ class Engine:
         as the packed weights"""
         gamma, beta = self.P(p + ".weight"), self.P(p + ".bias")
         rm, rv = self.P(p + ".running_mean"), self.P(p + ".running_var")
-        ver = self.stamp + tuple(t._version for t in (gamma, beta, rm, rv)) + tuple(t.data_ptr() for t in (gamma, beta, rm, rv))
+        # While a layer is frozen together with its weight and bias, no forward and no optimizer writes it: its pair outlives the step's stamp.
+        # Every forward that runs the layer in any other state (batch statistics, trainable weight / bias: writes that bump no tensor version)
+        # moves its generation, so a pair cached before such a period is never taken for the layer's state after it.
+        const = p in self.m.frozen_bn and not (gamma.requires_grad or beta.requires_grad)
+        if not const:
+            self.bn_gen[p] = self.bn_gen.get(p, 0) + 1
+        ver = (("c", self.bn_gen.get(p, 0)) if const else self.stamp) + tuple(t._version for t in (gamma, beta, rm, rv)) + tuple(t.data_ptr() for t in (gamma, beta, rm, rv))
         hit = self.bn_eval.get(p)
         if hit is None or hit[0] != ver:
             hit = (ver, ops.bn_scale_shift_eval(C, gamma.detach(), beta.detach(), rm, rv))
@@ -471,14 +501,16 @@ class Engine:
         """conv -> BatchNorm (-> + res) (-> ReLU), KGnet.py:82-97.  Inference (running statistics, nothing recorded): ONE launch -- the
         BatchNorm is a per-channel affine map of the conv's fp32 accumulators (kg_planes_t.oscale + bias; the conv output is never stored
         and re-read), residual and ReLU ride in the same epilogue.  Training: conv (+ statistics in its epilogue), then bn()."""
-        if self.tape is None and not self.m.training and self.fuse_eval_bn:
+        batch = self.bn_batch_stats(bnp)
+        if not batch and self.fuse_eval_bn and (self.tape is None or not self.trainable((bnp + ".weight", bnp + ".bias"))):
+            # (recorded forward: a BatchNorm frozen together with its weight and bias is a constant affine map -- same launch as inference)
             if out is None:
                 OH, OW = (H + 2 * s.pad - s.k) // s.stride + 1, (W + 2 * s.pad - s.k) // s.stride + 1
                 out = ops.alloc_pt(N * OH * OW, s.cout, self.bpt, xv.t.device, dtype=self.dt)
-            yv, OH, OW = self.conv(xv, s, N, H, W, relu, out=out, affine=self.bn_eval_affine(bnp, s.cout), res=res)
+            yv, OH, OW = self.conv(xv, s, N, H, W, relu, out=out, affine=self.bn_eval_affine(bnp, s.cout), res=res, frozen_bn=self.tape is not None)
             yv.gP = min(self.bpt, self.pg)
             return yv, OH, OW
-        y, OH, OW = self.conv(xv, s, N, H, W, False, bn_stats=bn_stats)
+        y, OH, OW = self.conv(xv, s, N, H, W, False, bn_stats=bn_stats and batch)
         return self.bn(y, bnp, relu, res=res, out=out), OH, OW
 
     def bn(self, xv, p, relu, res=None, out=None):
@@ -488,7 +520,9 @@ class Engine:
         rm, rv = self.P(p + ".running_mean"), self.P(p + ".running_var")
         if out is None:
             out = ops.alloc_pt(xv.rows, C, self.bpt, dev, dtype=self.dt)
-        if self.m.training:
+        batch = self.bn_batch_stats(p)
+        if batch:
+            self.bn_gen[p] = self.bn_gen.get(p, 0) + 1      # (the running statistics move: bn_eval_affine)
             bp = getattr(xv, "bn_part", None)
             if bp is not None:       # the producing conv's epilogue already summed the rows (conv_args.h): second stage only
                 mean, invstd, scale, shift = ops.bn_finalize_train(bp[0], bp[1], xv.rows, C, gamma.detach(), beta.detach(), rm, rv)
@@ -501,13 +535,34 @@ class Engine:
             scale, shift = self.bn_eval_affine(p, C)
             mean = invstd = None
         ops.bn_apply(xv.t, C, scale, shift, out, res=res.t if res is not None else None, relu=relu)
-        yv = Var(out, C, relu=relu, gP=min(self.bpt, self.pg))
+        affine_req = self.tape is not None and (gamma.requires_grad or beta.requires_grad)
+        yv = Var(out, C, relu=relu, req=xv.req or affine_req or (res is not None and res.req), gP=min(self.bpt, self.pg))
         xv.uses += 1
         if res is not None:
             res.uses += 1
-        if self.tape is not None:
-            if mean is None:
-                raise NotImplementedError("backward through eval-mode BatchNorm is not supported; call model.train()")
+        if self.tape is not None and yv.req and not batch:
+            # running statistics are constants: ONE pass gives dx = scale * g and the sums of dgamma / dbeta (yv.bn_in stays None: no input
+            # gradient arms the train-mode statistics epilogue for this layer)
+            def bwd_frozen():
+                g = yv.take_grad()
+                if g is None:
+                    return
+                if yv.boundary:
+                    self.renormalise(g, yv.C)
+                if affine_req or xv.req:
+                    dg = self.new_grad(p + ".weight", gamma) if affine_req else None
+                    db = self.new_grad(p + ".bias", beta) if affine_req else None
+                    dx = ops.alloc_pt(xv.rows, C, xv.gP, dev, dtype=self.dt)
+                    ops.bn_bwd_frozen(xv.t if affine_req else None, g, C, scale, rm, rv, dg, db, dx)
+                    if affine_req:
+                        self.param_grads[p + ".weight"] = dg
+                        self.param_grads[p + ".bias"] = db
+                    if xv.req:
+                        xv.add_grad(dx, masked=True)
+                if res is not None and res.req:
+                    res.add_grad(g, masked=False)
+            self.tape.append(bwd_frozen)
+        elif self.tape is not None and yv.req:
             yv.bn_in = (xv.t, mean, invstd)
 
             def bwd():
@@ -527,8 +582,9 @@ class Engine:
                 ops.bn_bwd(xv.t, g, C, gamma.detach(), mean, invstd, dg, db, dx, parts=bst, parts_scale=r if bst is not None else None)
                 self.param_grads[p + ".weight"] = dg
                 self.param_grads[p + ".bias"] = db
-                xv.add_grad(dx, masked=True)
-                if res is not None:
+                if xv.req:
+                    xv.add_grad(dx, masked=True)
+                if res is not None and res.req:
                     res.add_grad(g, masked=False)
             self.tape.append(bwd)
         return yv
@@ -537,11 +593,11 @@ class Engine:
         C = xv.C
         OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
         out = ops.alloc_pt(N * OH * OW, C, xv.P, xv.t.device, dtype=self.dt)
-        arg = torch.empty(N * OH * OW, C, dtype=torch.uint8, device=xv.t.device) if self.tape is not None else None
+        arg = torch.empty(N * OH * OW, C, dtype=torch.uint8, device=xv.t.device) if self.tape is not None and xv.req else None
         ops.maxpool_fwd(xv.t, out, N, H, W, C, argmax=arg)
         xv.uses += 1
-        yv = Var(out, C, relu=False, gP=xv.gP)
-        if self.tape is not None:
+        yv = Var(out, C, relu=False, req=xv.req, gP=xv.gP)
+        if self.tape is not None and xv.req:
             def bwd():
                 g = yv.take_grad()
                 if g is None:
@@ -557,8 +613,8 @@ class Engine:
         out = ops.alloc_pt(N * OH * OW, C, xv.P if P is None else P, xv.t.device, dtype=self.dt)
         ops.bilinear_fwd(xv.t, out, N, IH, IW, OH, OW, C)
         xv.uses += 1
-        yv = Var(out, C, relu=False, gP=min(out.P, self.pg))
-        if self.tape is not None:
+        yv = Var(out, C, relu=False, req=xv.req, gP=min(out.P, self.pg))
+        if self.tape is not None and xv.req:
             def bwd():
                 g = yv.take_grad()
                 if g is None:
@@ -571,17 +627,18 @@ class Engine:
 
     def concat(self, buf, parts):
         """buf = PT [rows, sum C]; parts = Vars whose .t are the column slices of buf (already written)."""
-        cv = Var(buf, buf.shape[1], relu=all(p.relu for p in parts), gP=max(p.gP for p in parts))
+        cv = Var(buf, buf.shape[1], relu=all(p.relu for p in parts), req=any(p.req for p in parts), gP=max(p.gP for p in parts))
         for p in parts:
             p.uses += 1
-        if self.tape is not None:
+        if self.tape is not None and cv.req:
             def bwd():
                 g = cv.take_grad()
                 if g is None:
                     return
                 c = 0
                 for p in parts:
-                    p.add_grad(g.cols(c, c + p.C), masked=cv.relu)
+                    if p.req:
+                        p.add_grad(g.cols(c, c + p.C), masked=cv.relu)
                     c += p.C
             self.tape.append(bwd)
         return cv
@@ -791,7 +848,8 @@ class Engine:
             self.kp_logits[lvl] = side[0]
         slot = {"grad": None}
         self.head_slots.append((slot, lvl, N, H, W))
-        if train:
+        wreq = [train and self.trainable((s.names[0] + ".weight", s.names[0] + ".bias")) for s in specs]
+        if train and (hid.req or any(wreq)):
             geom = (N * H * W, H, W, H, W, 7, 7, 1, 3)
 
             def bwd():
@@ -799,6 +857,8 @@ class Engine:
                 if g is None:
                     return
                 for k, ((h, co), s) in enumerate(zip(arch.HEADS, specs)):
+                    if not wreq[k]:
+                        continue
                     gk = g.cols(self.HEAD_OFF[k], self.HEAD_OFF[k] + self.HEAD_PAD[k])
                     w = self.P(s.names[0] + ".weight")
                     gw = self.new_grad(s.names[0] + ".weight", w)
@@ -806,6 +866,8 @@ class Engine:
                     ops.conv_wgrad(trunc(hid.t, min(hid.gP, self.pw)).cols(k * C, (k + 1) * C), trunc(gk, self.pw), C, co, geom, [(gw, 0, co)], N=N, bias_out=db)
                     self.param_grads[s.names[0] + ".weight"] = gw
                     self.param_grads[s.names[0] + ".bias"] = db
+                if not hid.req:
+                    return
                 dh = ops.alloc_pt(hid.rows, 3 * C, hid.gP, dev, dtype=self.dt)
                 # kp / short cout blocks only see dY channels 0..23 (k-step 1 of the chunk skipped); mid sees 24..63
                 if pwN is not None and g.P == 1 and NARROW_HEADS_DGRAD >= 2 and dh.P == 1:
@@ -862,7 +924,7 @@ class Engine:
                     ops.grad_pack(g.contiguous().float(), prob, view, N, co, Hh, Wh, self.HEAD_PAD[k], scale=gsc)
             slot["grad"] = packed
         for fv, g in zip(self.feats, feat_grads):
-            if g is None:
+            if g is None or not fv.req:          # (not fv.req: nothing trainable upstream of this feature map)
                 continue
             if isinstance(g, PT):              # the fused forward's seg backward already wrote split-bf16 rows
                 fv.add_grad(g, masked=False)

@@ -784,6 +784,17 @@ def bn_bwd(x, dy, C, gamma, mean, invstd, dgamma, dbeta, dx, accumulate=False, p
               pl(a=x, b=dy, y=dx), stream_ptr(), fmt=fmt_of(x))
 
 
+def bn_bwd_frozen(x, dy, C, scale, rmean, rvar, dgamma, dbeta, dx, accumulate=False, eps=1e-5):
+    """Backward of a BatchNorm on its running statistics (kg_bn_bwd_frozen): dx = scale * dy and, in the same pass over x and dy,
+    dbeta = sum dy, dgamma = sum dy * (x - rmean) * rsqrt(rvar + eps).  dgamma = dbeta = None: dx alone (x, rmean, rvar may be None)."""
+    if (dgamma is None) != (dbeta is None):
+        raise ValueError("bn_bwd_frozen: dgamma and dbeta come together")
+    sc = scratch_f32(2 * C * 512 + 3 * C, base(dy).device, "bn") if dgamma is not None else None
+    _lib.call("kg_bn_bwd_frozen", ptr(base(x)), ld(x) if x is not None else 0, ptr(_rows(dy)), ld(dy), ptr(scale), ptr(rmean), ptr(rvar),
+              c_float(eps), ptr(dgamma), ptr(dbeta), 1 if accumulate else 0, ptr(_rows(dx)), ld(dx), base(dy).shape[0], C, ptr(sc),
+              sc.numel() if sc is not None else 0, pl(a=x, b=dy, y=dx), stream_ptr(), fmt=fmt_of(dy))
+
+
 def maxpool_fwd(x, y, N, H, W, C, argmax=None):
     """argmax (optional uint8 [N*OH*OW, C]): receives the winning tap of every output element for maxpool_bwd."""
     _lib.call("kg_maxpool3s2_fwd", ptr(_rows(x)), ld(x), ptr(_rows(y)), ld(y), ptr(argmax), N, H, W, C, pl(a=x, y=y), stream_ptr(), fmt=fmt_of(x))
