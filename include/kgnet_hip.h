@@ -354,6 +354,24 @@ int kg_mask_unpack_bits(const void* words, long ld_words, int n, int H, int W, v
 int kg_bitmask_areas(const void* words, int n, long ld_words, int* area, void* stream);
 int kg_bitmask_inter_pairs(const void* a, int na, const void* b, int nb, const int* pairs, int npairs, long ld_words, int* inter,
                            void* stream);
+/* Instance results from the words (csrc/instances.hip).  Input: the masks of nimg images of one size H x W, rows concatenated; image i
+ * owns rows [row_start[i], row_start[i + 1]) -- row_start is a HOST array of nimg + 1 ints, row_start[0] == 0, non-decreasing,
+ * row_start[nimg] == n (what predict(packed=True) and inference.image_row_ranges produce).  Row order is priority order.
+ * kg_instance_labels: labels = device int32 [nimg][H][W], 0 where no row of the image covers the pixel, else the id of the first covering
+ * row: ids[row] (device int32 [n], values only) or, with ids == NULL, row - row_start[i] + 1.  table (optional) = device int64 [n][8], one
+ * line per row: {area_full, area_visible, y1, x1, y2, x2, sum_y, sum_x} -- set bits of the row, pixels of the label map the row won,
+ * their half-open bounding box (0, 0, 0, 0 if none) and their coordinate sums; exact integers.
+ * kg_instance_overlay: apply_mask (test.py:29-37) for every row of an image in ascending row order, on image = device bytes
+ * [nimg][H][W][3] into out (same shape, may equal image): every covered channel becomes (uint8)(v * (1 - alpha) + alpha * color[c] * 255)
+ * in float64, truncated; colors = device float64 [n][3] in [0, 1], alpha in [0, 1].
+ * Both write every element of labels / table / out (an image without rows: zeros / the image itself; n == 0 is valid), launch a number
+ * of kernels that does not depend on n (one per 256 images and output), never synchronise, and validate on the host before any HIP call:
+ * null pointers, H, W > 0, n >= 0, nimg > 0, ld_words, 16-byte alignment of words, row_start, nimg * H * W <= 2^31 - 1.  No kernel uses
+ * a value read from device memory as an index. */
+int kg_instance_labels(const void* words, long ld_words, int n, const int* row_start, int nimg, int H, int W, const int* ids, int* labels,
+                       long long* table, void* stream);
+int kg_instance_overlay(const void* image, const void* words, long ld_words, int n, const int* row_start, int nimg, int H, int W,
+                        const double* colors, double alpha, void* out, void* stream);
 
 /* ---- per-box segmentation branch (KGnet.py:246-267, 321-350): ragged row bookkeeping ---- */
 int kg_seg_build_rows(const int* boxtab8, int nb, int* rowdesc, int* row2box, int* srcrow, void* stream);

@@ -87,3 +87,40 @@ def _empty(hw, device_u8, dev, packed=False):
         return [BitMasks.empty(h, w, dev), np.zeros((0, 5), np.float32)]
     m = torch.empty(0, h, w, dtype=torch.uint8, device=dev) if device_u8 else np.zeros((0, h, w), np.float32)
     return [m, np.zeros((0, 5), np.float32)]
+
+
+def instances_from_predictions(preds):
+    """predict(packed=True)'s list -> per image None or an instances.Instances (labels: device int32 [h, w], dets: predict's, table: host
+    int64 [n, 8], masks: the BitMasks).  One kg_instance_labels call per distinct output size, with all images of that size in it, and one
+    device -> host copy of all tables."""
+    from . import instances
+    out = [None] * len(preds)
+    todo = [i for i, p in enumerate(preds) if p is not None]
+    if not todo:
+        return out
+    tables, where = [], []
+    for _, imgs in size_groups([preds[i][0].shape[1:] for i in todo]):
+        imgs = [todo[j] for j in imgs]
+        parts = [preds[i][0] for i in imgs]
+        if parts[0].device.type != "cuda":
+            raise _lib.KGLibraryError("predict_instances (MI355X build) needs masks on a GPU device")
+        row_start = np.concatenate([[0], np.cumsum([len(p) for p in parts])])
+        labels, table = instances.label_map(instances.join_masks(parts), row_start)
+        tables.append(table)
+        for k, i in enumerate(imgs):
+            out[i] = instances.Instances(labels[k], preds[i][1], None, preds[i][0])
+            where.append(i)
+    host = torch.cat(tables).cpu().numpy() if len(tables) > 1 else tables[0].cpu().numpy()
+    r = 0
+    for i in where:
+        out[i].table = host[r:r + len(out[i].masks)]
+        r += len(out[i].masks)
+    return out
+
+
+def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None, max_workspace_bytes=None):
+    """predict(packed=True) followed by the instance label map and the per-instance table of every image (instances.py), on the device:
+    the label map (4 bytes per pixel) and the table (64 bytes per instance) replace n full-size masks as what crosses to the host."""
+    if not torch.is_tensor(x) or x.device.type != "cuda":
+        raise _lib.KGLibraryError("predict_instances (MI355X build) needs the input batch on a GPU device")
+    return instances_from_predictions(predict(model, x, nms_thresh, seg_thresh, image_sizes, max_workspace_bytes=max_workspace_bytes, packed=True))
