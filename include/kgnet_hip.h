@@ -372,6 +372,26 @@ int kg_instance_labels(const void* words, long ld_words, int n, const int* row_s
                        long long* table, void* stream);
 int kg_instance_overlay(const void* image, const void* words, long ld_words, int n, const int* row_start, int nimg, int H, int W,
                         const double* colors, double alpha, void* out, void* stream);
+/* Tiled whole-image inference (csrc/tiling.hip; tiling.py states the semantics in NumPy).  A grid is ny x nx tiles of th x tw pixels;
+ * ys / xs are HOST arrays of the tile origins along each axis: 1 .. 256 entries, ys[0] >= 0, strictly ascending, the last below H (W).
+ * Tile t = r * nx + c.  A tile may reach past the image.
+ * kg_tile_cut: image = device bytes [H][W][3] -> out = device float32 [ny * nx][3][th][tw] (16-byte aligned, tw % 4 == 0), every element
+ * written: float32(byte) / 255 - 0.5 in two float32 operations, channels in the image's order; a pixel outside the image is -0.5.
+ * kg_bitmask_clip: clears in place every bit at y >= vh or x >= vw of n masks in the bit-mask layout (0 <= vh <= H, 0 <= vw <= W); the
+ * padding word and rows >= n are not touched; vh == H && vw == W and n == 0 launch nothing.
+ * kg_tile_stitch: tile_labels = device int32 [ny * nx][th][tw], values >= 0 -> labels = device int32 [H][W], every element written once:
+ * the smallest non-zero value over the tiles that cover the pixel, 0 if there is none.  A gather: no atomics, no read of labels.
+ * kg_label_table: jobs = device int32 [n][5] rows {id, y1, x1, y2, x2}, written and validated by the caller (0 <= y1 <= y2 <= H, the same
+ * for x, id > 0; the kernel clamps the box to the map before it forms an address) -> table = device int64 [n][8], every element written:
+ * {area_full[j] (device int64 [n]; 0 when NULL), then over the pixels of the box with labels == id: count, y1, x1, y2, x2 (half-open,
+ * zeros if none), sum_y, sum_x}; n == 0 is valid.
+ * All four validate on the host before any HIP call (null pointers, sizes, ny * nx * th * tw and H * W <= 2^31 - 1, alignment, the
+ * origins), never synchronise, and use values read from device memory as stored values and predicates only. */
+int kg_tile_cut(const void* image, int H, int W, const int* ys, int ny, const int* xs, int nx, int th, int tw, float* out, void* stream);
+int kg_bitmask_clip(void* words, long ld_words, int n, int H, int W, int vh, int vw, void* stream);
+int kg_tile_stitch(const int* tile_labels, const int* ys, int ny, const int* xs, int nx, int th, int tw, int H, int W, int* labels,
+                   void* stream);
+int kg_label_table(const int* labels, int H, int W, const int* jobs, int n, const long long* area_full, long long* table, void* stream);
 
 /* ---- per-box segmentation branch (KGnet.py:246-267, 321-350): ragged row bookkeeping ---- */
 int kg_seg_build_rows(const int* boxtab8, int nb, int* rowdesc, int* row2box, int* srcrow, void* stream);

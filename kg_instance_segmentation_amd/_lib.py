@@ -100,6 +100,10 @@ _SIGS = {
     "kg_bitmask_inter_pairs": [P, c_int, P, c_int, P, c_int, c_long, P, P],
     "kg_instance_labels": [P, c_long, c_int, P, c_int, c_int, c_int, P, P, P, P],
     "kg_instance_overlay": [P, P, c_long, c_int, P, c_int, c_int, c_int, P, c_double, P, P],
+    "kg_tile_cut": [P, c_int, c_int, P, c_int, P, c_int, c_int, c_int, P, P],
+    "kg_bitmask_clip": [P, c_long, c_int, c_int, c_int, c_int, c_int, P],
+    "kg_tile_stitch": [P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, P, P],
+    "kg_label_table": [P, c_int, c_int, P, c_int, P, P, P],
     "kg_f64_probe": [P, P, P, c_int, P],
     "kg_seg_build_rows": [P, c_int, P, P, P, P],
     "kg_seg_build_rows_levels": [c_int, P, P, P, P, P, P],

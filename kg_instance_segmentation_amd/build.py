@@ -42,6 +42,7 @@ SOURCES = {
     "conv3_ws.hip": [],
     "conv7_narrow.hip": [],
     "instances.hip": ["-ffp-contract=off"],
+    "tiling.hip": ["-ffp-contract=off"],
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function"]

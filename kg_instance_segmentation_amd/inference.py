@@ -124,3 +124,6 @@ def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None
     if not torch.is_tensor(x) or x.device.type != "cuda":
         raise _lib.KGLibraryError("predict_instances (MI355X build) needs the input batch on a GPU device")
     return instances_from_predictions(predict(model, x, nms_thresh, seg_thresh, image_sizes, max_workspace_bytes=max_workspace_bytes, packed=True))
+
+
+from .tiling import predict_tiled  # noqa: E402,F401  (whole images of any size at native resolution: tiling.py)

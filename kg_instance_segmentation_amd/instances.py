@@ -162,18 +162,33 @@ def _device_masks(fn, masks):
     return masks
 
 
-def label_map(masks, row_start=None, priority=None, with_table=True):
+def label_map(masks, row_start=None, priority=None, with_table=True, ids=None):
     """BitMasks of one or more images of one size -> (labels device int32 [nimg, H, W], table device int64 [n, 8] or None).
     row_start: host ints [nimg + 1], image i owns rows [row_start[i], row_start[i + 1]) (default: one image holding all rows).
     priority: host int array over all rows, within every image a permutation of that image's rows, highest priority first (default:
-    row order).  Ids and table lines always refer to the rows of `masks` as given."""
+    row order).  Ids and table lines always refer to the rows of `masks` as given.
+    ids: host int32 [n] (or a device int32 tensor [n]), the value written for every row instead of its index within its image + 1
+    (tiling.py: the ids of a whole image's instances in the label map of one tile); it cannot be given together with priority."""
     import torch
     from ._lib import ptr, stream_ptr, c_long
     masks = _device_masks("label_map", masks)
     n, h, w = masks.shape
     rs = _ranges(row_start, n)
     nimg = len(rs) - 1
-    ids = prio = None
+    prio = None
+    if ids is not None:
+        if priority is not None:
+            raise _lib.KGLibraryError("label_map: ids cannot be given together with priority")
+        if torch.is_tensor(ids):
+            if ids.dtype != torch.int32 or ids.device != masks.device or tuple(ids.shape) != (n,):
+                raise _lib.KGLibraryError(f"label_map: device ids must be int32 [{n}] on the masks' device")
+            ids = ids.contiguous() if n else None
+        else:
+            v = np.asarray(ids)
+            if v.shape != (n,) or v.dtype.kind not in "iu" or (n and (v.min() < -2 ** 31 or v.max() > 2 ** 31 - 1)):
+                raise _lib.KGLibraryError(f"label_map: ids must be {n} integers that fit int32")
+            from . import ops
+            ids = ops.h2d(np.ascontiguousarray(v.astype(np.int32)), masks.device) if n else None
     if priority is not None:
         p = np.asarray(priority, np.int64).reshape(-1)
         if len(p) != n:
