@@ -392,6 +392,25 @@ int kg_bitmask_clip(void* words, long ld_words, int n, int H, int W, int vh, int
 int kg_tile_stitch(const int* tile_labels, const int* ys, int ny, const int* xs, int nx, int th, int tw, int H, int W, int* labels,
                    void* stream);
 int kg_label_table(const int* labels, int H, int W, const int* jobs, int n, const long long* area_full, long long* table, void* stream);
+/* Label-map evaluation (csrc/labelmetrics.hip; labelmetrics.py states the semantics in NumPy): the contingency of two instance label
+ * maps -- the area of every id of either map and the pixel count of every (id_a, id_b) pair that meets -- from which the Kaggle score,
+ * AJI, PQ, Dice and the reference's AP are computed on the host.
+ * kg_label_stats: labels = device int32 [H][W] with ids 1 .. n (0 = background) -> stats = device int32 [n][5], row id - 1 =
+ * {area, y1, x1, y2, x2} of the pixels equal to id (half-open box; zeros for an id with no pixel), and invalid[0] = the number of pixels
+ * whose value lies outside [0, n].  This is the ONE entry of the family that forms an address from a value read from device memory, and
+ * the rule that bounds it is: the index v - 1 is formed only inside the predicate (unsigned)(v - 1) < (unsigned)n (unsigned arithmetic,
+ * so no value wraps into range); a pixel that fails it adds one to invalid and touches nothing else, and the stats of every valid id
+ * are exact whatever the other pixels hold.  Three launches (init, walk, finish) whatever n is; the walk issues integer atomics (add,
+ * min, max) once per run of equal labels inside a 64-pixel row segment, so the result does not depend on arrival order.  n == 0 is
+ * valid (stats may then be NULL): every non-zero pixel is invalid.
+ * kg_label_inter_jobs: a, b = device int32 [H][W]; jobs = device int32 [m][6] rows {id_a, id_b, y1, x1, y2, x2}, written by the caller
+ * -> count = device int64 [m], count[j] = the pixels of the box with a == id_a && b == id_b.  One workgroup per job; the box is clamped
+ * to the map before any address is formed (an empty or inverted box gives 0), labels are predicates only, no atomics.  m == 0 is valid
+ * and launches nothing.
+ * Both validate on the host before any HIP call (null pointers, H, W > 0, H * W <= 2^31 - 1, n, m >= 0, 4-byte alignment, 8 bytes for
+ * count), never synchronise and write every output element. */
+int kg_label_stats(const int* labels, int H, int W, int n, int* stats, int* invalid, void* stream);
+int kg_label_inter_jobs(const int* a, const int* b, int H, int W, const int* jobs, int m, long long* count, void* stream);
 
 /* ---- per-box segmentation branch (KGnet.py:246-267, 321-350): ragged row bookkeeping ---- */
 int kg_seg_build_rows(const int* boxtab8, int nb, int* rowdesc, int* row2box, int* srcrow, void* stream);

@@ -104,6 +104,8 @@ _SIGS = {
     "kg_bitmask_clip": [P, c_long, c_int, c_int, c_int, c_int, c_int, P],
     "kg_tile_stitch": [P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, P, P],
     "kg_label_table": [P, c_int, c_int, P, c_int, P, P, P],
+    "kg_label_stats": [P, c_int, c_int, c_int, P, P, P],
+    "kg_label_inter_jobs": [P, P, c_int, c_int, P, c_int, P, P],
     "kg_f64_probe": [P, P, P, c_int, P],
     "kg_seg_build_rows": [P, c_int, P, P, P, P],
     "kg_seg_build_rows_levels": [c_int, P, P, P, P, P, P],

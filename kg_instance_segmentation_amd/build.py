@@ -43,6 +43,7 @@ SOURCES = {
     "conv7_narrow.hip": [],
     "instances.hip": ["-ffp-contract=off"],
     "tiling.hip": ["-ffp-contract=off"],
+    "labelmetrics.hip": [],
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function"]
