@@ -411,6 +411,41 @@ int kg_label_table(const int* labels, int H, int W, const int* jobs, int n, cons
  * count), never synchronise and write every output element. */
 int kg_label_stats(const int* labels, int H, int W, int n, int* stats, int* invalid, void* stream);
 int kg_label_inter_jobs(const int* a, const int* b, int H, int W, const int* jobs, int m, long long* count, void* stream);
+/* Label-map clean-up (csrc/components.hip; components.py states the semantics in NumPy): connected components of label maps, what the
+ * host needs to decide about them, and the decision written back.
+ * kg_label_components: labels = device int32 [nimg][H][W], ANY int32 values (compared only, never an index).  Two pixels of one image
+ * belong together if they hold the same value and are adjacent under the rule for that value: `connectivity` (4 or 8) for non-zero
+ * values, `bg_connectivity` (0, 4 or 8) for the value 0; with bg_connectivity == 0 zero pixels belong to no component.  comp = device
+ * int32 [nimg][H][W]: 0 for a pixel outside every component, else the number of its component, 1 .. m_i per image in raster order of
+ * each component's first pixel (smallest y * W + x); ncomp = device int32 [nimg] = m_i.  Images are independent.  workspace = device
+ * memory of at least kg_label_components_workspace_bytes (nimg, H, W) bytes (host helper; -1 on bad arguments), 4-byte aligned, contents
+ * irrelevant on entry.  Six launches whatever the maps hold.
+ * kg_component_stats: comp_start = HOST array of nimg + 1 ints, the prefix sums of ncomp the caller read back (comp_start[0] == 0, non-
+ * decreasing, comp_start[nimg] == total) -> stats = device int32 [total][9], row comp_start[i] + c - 1 = {value, area, y1, x1, y2, x2,
+ * border, nb_min, nb_max}: the label value of the component, its pixel count, its half-open box, border = 1 if a pixel lies on the first
+ * or last row or column of its image, and the smallest and largest comp value over all 4-adjacent pixels of the same image whose comp
+ * differs from c (pixels with comp == 0 count as 0; both -1 if there is none).  Integer atomics (add, min, max, or) at most once per run of equal
+ * comp values inside a 64-pixel row segment -- one that cannot change its cell is skipped, and each wave folds the runs of one component
+ * it meets segment after segment before it commits them -- so arrival order cannot change the result; a row no pixel names is {0, 0, 0, 0, 0, 0, 0, -1, -1}.  total == 0
+ * is valid (stats may then be NULL).  Two launches plus one per 256 images.
+ * kg_component_remap: newval = device int32 [total] -> out = device int32 [nimg][H][W] = newval[comp_start[i] + c - 1] where comp == c > 0,
+ * 0 elsewhere; out may alias neither input.  One launch per 256 images.
+ * All three validate on the host before any HIP call (null pointers, nimg, H, W > 0, nimg * H * W <= 2^31 - 1, the connectivities, the
+ * workspace size, 4-byte alignment, comp_start), never synchronise and write every output element.
+ * INDEX RULE.  This family is the second exception (after kg_label_stats) to "no kernel uses a value read from device memory as an
+ * index": union-find cannot avoid it.  The parent array lives in `workspace`; the entry's own first kernel writes the whole array before
+ * any kernel reads it; it only ever holds linear pixel indices of the same image, written by these kernels; a parent never exceeds its
+ * own index (atomicMin only lowers values), so every find loop descends strictly; every dereference of a value v read from memory still
+ * sits inside the predicate (unsigned)v < (unsigned)(H * W); every find and union loop also has a hard iteration bound.
+ * kg_component_stats and kg_component_remap index by c - 1 only inside (unsigned)(c - 1) < (unsigned)m_i: a comp value that fails the
+ * predicate touches nothing and writes 0.  The root of a set is its smallest linear index, so comp and ncomp are the same whatever
+ * order the atomics land in. */
+long kg_label_components_workspace_bytes(int nimg, int H, int W);
+int kg_label_components(const int* labels, int nimg, int H, int W, int connectivity, int bg_connectivity, int* comp, int* ncomp,
+                        void* workspace, long workspace_bytes, void* stream);
+int kg_component_stats(const int* labels, const int* comp, int nimg, int H, int W, const int* comp_start, int total, int* stats,
+                       void* stream);
+int kg_component_remap(const int* comp, int nimg, int H, int W, const int* comp_start, int total, const int* newval, int* out, void* stream);
 
 /* ---- per-box segmentation branch (KGnet.py:246-267, 321-350): ragged row bookkeeping ---- */
 int kg_seg_build_rows(const int* boxtab8, int nb, int* rowdesc, int* row2box, int* srcrow, void* stream);

@@ -106,6 +106,10 @@ _SIGS = {
     "kg_label_table": [P, c_int, c_int, P, c_int, P, P, P],
     "kg_label_stats": [P, c_int, c_int, c_int, P, P, P],
     "kg_label_inter_jobs": [P, P, c_int, c_int, P, c_int, P, P],
+    "kg_label_components_workspace_bytes": [c_int, c_int, c_int],
+    "kg_label_components": [P, c_int, c_int, c_int, c_int, c_int, P, P, P, c_long, P],
+    "kg_component_stats": [P, P, c_int, c_int, c_int, P, c_int, P, P],
+    "kg_component_remap": [P, c_int, c_int, c_int, P, c_int, P, P, P],
     "kg_f64_probe": [P, P, P, c_int, P],
     "kg_seg_build_rows": [P, c_int, P, P, P, P],
     "kg_seg_build_rows_levels": [c_int, P, P, P, P, P, P],
@@ -121,7 +125,7 @@ _SIGS = {
     "kg_crop_grad_reduce": [P, c_int, P, c_int, c_long, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P],
 }
 _RESTYPE = {"kg_postproc_workspace_bytes": c_long, "kg_postproc_batch_workspace_bytes": c_long, "kg_nms_batch_workspace_bytes": c_long,
-            "kg_mask_bits_ld": c_long}
+            "kg_mask_bits_ld": c_long, "kg_label_components_workspace_bytes": c_long}
 SYMBOLS = tuple(_SIGS) + ("kg_last_error", "kg_last_kernel")
 
 _lib = None

@@ -44,6 +44,7 @@ SOURCES = {
     "instances.hip": ["-ffp-contract=off"],
     "tiling.hip": ["-ffp-contract=off"],
     "labelmetrics.hip": [],
+    "components.hip": [],
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function"]

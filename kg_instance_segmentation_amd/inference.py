@@ -118,12 +118,18 @@ def instances_from_predictions(preds):
     return out
 
 
-def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None, max_workspace_bytes=None):
+def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None, max_workspace_bytes=None, clean=None):
     """predict(packed=True) followed by the instance label map and the per-instance table of every image (instances.py), on the device:
-    the label map (4 bytes per pixel) and the table (64 bytes per instance) replace n full-size masks as what crosses to the host."""
+    the label map (4 bytes per pixel) and the table (64 bytes per instance) replace n full-size masks as what crosses to the host.
+    clean: None, or a dict of components.clean's policy arguments: every label map is then cleaned on the device (one components pass
+    over all images of one output size) and the tables are refreshed."""
     if not torch.is_tensor(x) or x.device.type != "cuda":
         raise _lib.KGLibraryError("predict_instances (MI355X build) needs the input batch on a GPU device")
-    return instances_from_predictions(predict(model, x, nms_thresh, seg_thresh, image_sizes, max_workspace_bytes=max_workspace_bytes, packed=True))
+    out = instances_from_predictions(predict(model, x, nms_thresh, seg_thresh, image_sizes, max_workspace_bytes=max_workspace_bytes, packed=True))
+    if clean is None:
+        return out
+    from . import components
+    return components.clean_instances_batch(out, **dict(clean))
 
 
 from .tiling import predict_tiled  # noqa: E402,F401  (whole images of any size at native resolution: tiling.py)

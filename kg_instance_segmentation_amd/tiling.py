@@ -415,13 +415,18 @@ def table_from_labels(labels, jobs, area_full=None):
     return table
 
 
-def assemble(plan, per_tile_preds, nms_thresh=0.5, device=None, stage=None):
+def assemble(plan, per_tile_preds, nms_thresh=0.5, device=None, stage=None, clean=None):
     """Everything after the per-tile predict calls.  per_tile_preds: per tile None or predict(packed=True)'s [BitMasks of th x tw, dets];
     the masks of a tile that reaches past the image are clipped in place.  device: where an empty result's labels go when no tile has a
     detection (default: the masks' device, else the current GPU).  stage: optional callable(name), called on the stream before the label
     launches, the stitch, the table and at the end (tools/tiling_bench.py puts device events there).
     Host <-> device traffic: ONE upload (the job table, with the ids and the row indices of the two mask gathers behind it) and ONE
-    device -> host copy (the global table)."""
+    device -> host copy (the global table).
+    clean: None, or a dict of components.clean's policy arguments: the stitched map then goes through components.clean_instances (its
+    launches and copies on top)."""
+    if clean is not None:
+        from . import components
+        return components.clean_instances(assemble(plan, per_tile_preds, nms_thresh, device, stage), **dict(clean))
     import torch
     from . import ops
     mark = stage if stage is not None else (lambda name: None)
@@ -476,11 +481,12 @@ def assemble(plan, per_tile_preds, nms_thresh=0.5, device=None, stage=None):
     return TiledInstances(labels, sel.dets, host, sel.tile, sel.origin, tile_masks)
 
 
-def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thresh=0.5, seg_thresh=0.5, max_workspace_bytes=None, stage=None):
+def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thresh=0.5, seg_thresh=0.5, max_workspace_bytes=None, stage=None,
+                  clean=None):
     """Instance segmentation of a whole image at native resolution -> TiledInstances.  image: host uint8 [H, W, 3] (uploaded once, to the
     model's device) or a device uint8 tensor; tile: the network input size, (th, tw) or one int, multiples of 32; overlap: pixels two
     neighbouring tiles share at least (choose it at least as large as the largest object: an object is cut at the edge of the tile that
-    owns its centre); batch: tiles per predict call."""
+    owns its centre); batch: tiles per predict call; clean: None, or a dict of components.clean's policy arguments (assemble)."""
     import torch
     from . import inference
     if int(batch) < 1:
@@ -499,4 +505,4 @@ def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thres
     preds = []
     for a in range(0, len(pl), int(batch)):
         preds += inference.predict(model, x[a:a + int(batch)], nms_thresh, seg_thresh, None, max_workspace_bytes=max_workspace_bytes, packed=True)
-    return assemble(pl, preds, nms_thresh, dev, stage)
+    return assemble(pl, preds, nms_thresh, dev, stage, clean)
