@@ -446,6 +446,29 @@ int kg_label_components(const int* labels, int nimg, int H, int W, int connectiv
 int kg_component_stats(const int* labels, const int* comp, int nimg, int H, int W, const int* comp_start, int total, int* stats,
                        void* stream);
 int kg_component_remap(const int* comp, int nimg, int H, int W, const int* comp_start, int total, const int* newval, int* out, void* stream);
+/* Per-instance measurements (csrc/measure.hip; measure.py states the semantics in NumPy): the exact integers every shape, contact and
+ * intensity measurement of an instance is a function of; the host derives centroid, axes, orientation, perimeter, mean and std from them.
+ * kg_label_measure: labels = device int32 [nimg][H][W], ANY int32 values (compared only); image = device [nimg][H][W][channels] of unsigned
+ * elements of elem_bytes bytes (1 or 2), NULL exactly when channels == 0; jobs = device int32 [m][6] rows {img, id, y1, x1, y2, x2}
+ * (half-open box), written by the caller -> out = device int64 [m][10 + 4 * channels], every element written.  With P = the pixels of the
+ * box, clamped to the map, of image img with labels == id, a row is {area = |P|; sum_y, sum_x, sum_yy, sum_yx, sum_xx over P of the pixel
+ * coordinates in the image; edges = the (pixel of P, direction up / down / left / right) pairs whose neighbour lies outside the map or
+ * holds a value != id; edges_border = those whose neighbour lies outside the map; edges_contact = those whose neighbour lies inside the
+ * map and holds a non-zero value != id; boundary_pixels = the pixels of P with at least one such edge; then per channel c: sum_c, sumsq_c,
+ * min_c, max_c over P (min and max 0 when area == 0)}.  Neighbours are read from the MAP, never from the box: a box edge inside the map
+ * is not an object edge, so the rows of bands that tile a box add up (min / max over the bands with area > 0) to the row of the box.
+ * SIZE RULE.  H, W <= 32768, so area <= 2^30, a coordinate product < 2^30, a coordinate sum < 2^60 and a 16-bit sum of squares < 2^62:
+ * every column fits int64; larger maps are refused.
+ * INDEX RULE.  No value read from device memory becomes an index: the job table is the one device-read table, its box is clamped to the
+ * map before any address is formed and its image index is used only inside (unsigned)img < (unsigned)nimg (a job that fails it, or whose
+ * box is empty or inverted, writes a row of zeros); labels and pixel values are predicates and summands only; a neighbour outside the map
+ * is decided by a predicate on its coordinates before its address exists.
+ * One launch whatever m is (one workgroup per job, no atomics); m == 0 is valid and launches nothing (jobs and out may then be NULL).
+ * Validates on the host before any HIP call (null pointers, nimg, H, W > 0, the size rule, nimg * H * W <= 2^31 - 1, channels in 0 .. 4,
+ * elem_bytes in {1, 2} whatever channels is, m >= 0, 4-byte alignment of labels and jobs, 8 of out, 2 of a 2-byte image) and never
+ * synchronises. */
+int kg_label_measure(const int* labels, int nimg, int H, int W, const void* image, int channels, int elem_bytes, const int* jobs, int m,
+                     long long* out, void* stream);
 
 /* ---- per-box segmentation branch (KGnet.py:246-267, 321-350): ragged row bookkeeping ---- */
 int kg_seg_build_rows(const int* boxtab8, int nb, int* rowdesc, int* row2box, int* srcrow, void* stream);

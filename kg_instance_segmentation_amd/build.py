@@ -45,6 +45,7 @@ SOURCES = {
     "tiling.hip": ["-ffp-contract=off"],
     "labelmetrics.hip": [],
     "components.hip": [],
+    "measure.hip": [],
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function"]

@@ -118,18 +118,24 @@ def instances_from_predictions(preds):
     return out
 
 
-def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None, max_workspace_bytes=None, clean=None):
+def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None, max_workspace_bytes=None, clean=None, measure=None):
     """predict(packed=True) followed by the instance label map and the per-instance table of every image (instances.py), on the device:
     the label map (4 bytes per pixel) and the table (64 bytes per instance) replace n full-size masks as what crosses to the host.
     clean: None, or a dict of components.clean's policy arguments: every label map is then cleaned on the device (one components pass
-    over all images of one output size) and the tables are refreshed."""
+    over all images of one output size) and the tables are refreshed.
+    measure: None; True: every result's `measurements` holds the geometry of its instances (measure.py), measured on the final label
+    map; or a uint8 / uint16 [N, h, w, C] array or device tensor at the label maps' size: the intensity columns too.  One launch for
+    all images of one output size."""
     if not torch.is_tensor(x) or x.device.type != "cuda":
         raise _lib.KGLibraryError("predict_instances (MI355X build) needs the input batch on a GPU device")
     out = instances_from_predictions(predict(model, x, nms_thresh, seg_thresh, image_sizes, max_workspace_bytes=max_workspace_bytes, packed=True))
-    if clean is None:
-        return out
-    from . import components
-    return components.clean_instances_batch(out, **dict(clean))
+    if clean is not None:
+        from . import components
+        out = components.clean_instances_batch(out, **dict(clean))
+    if measure is not None and measure is not False:
+        from . import measure as _measure
+        _measure.measure_instances_batch(out, None if measure is True else measure)
+    return out
 
 
 from .tiling import predict_tiled  # noqa: E402,F401  (whole images of any size at native resolution: tiling.py)

@@ -26,11 +26,12 @@ TABLE_COLUMNS = ("area_full", "area_visible", "y1", "x1", "y2", "x2", "sum_y", "
 
 class Instances:
     """One image's result of inference.predict_instances: labels = device int32 [h, w]; dets = float32 [n, 5], predict's; table = host
-    int64 [n, 8] (TABLE_COLUMNS); masks = the BitMasks."""
-    __slots__ = ("labels", "dets", "table", "masks")
+    int64 [n, 8] (TABLE_COLUMNS); masks = the BitMasks; measurements = None unless asked for (measure=, measure.py: a Measurements)."""
+    __slots__ = ("labels", "dets", "table", "masks", "measurements")
 
     def __init__(self, labels, dets, table, masks):
         self.labels, self.dets, self.table, self.masks = labels, dets, table, masks
+        self.measurements = None
 
     def __len__(self):
         return len(self.dets)

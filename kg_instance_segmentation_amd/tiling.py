@@ -482,11 +482,13 @@ def assemble(plan, per_tile_preds, nms_thresh=0.5, device=None, stage=None, clea
 
 
 def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thresh=0.5, seg_thresh=0.5, max_workspace_bytes=None, stage=None,
-                  clean=None):
+                  clean=None, measure=False):
     """Instance segmentation of a whole image at native resolution -> TiledInstances.  image: host uint8 [H, W, 3] (uploaded once, to the
     model's device) or a device uint8 tensor; tile: the network input size, (th, tw) or one int, multiples of 32; overlap: pixels two
     neighbouring tiles share at least (choose it at least as large as the largest object: an object is cut at the edge of the tile that
-    owns its centre); batch: tiles per predict call; clean: None, or a dict of components.clean's policy arguments (assemble)."""
+    owns its centre); batch: tiles per predict call; clean: None, or a dict of components.clean's policy arguments (assemble);
+    measure: with True the result's `measurements` holds measure.measure_instances of the final (cleaned, if clean is given) label map
+    against the uploaded uint8 image -- one more launch, one more upload (the jobs) and one more device -> host copy (the rows)."""
     import torch
     from . import inference
     if int(batch) < 1:
@@ -496,6 +498,9 @@ def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thres
         shape, dev = tuple(image.shape), image.device
     else:
         shape, dev = _host_image(image).shape, next(model.parameters()).device
+        if measure:                                                   # the one upload serves the tiles and the measurements
+            from . import ops
+            image = ops.h2d(_host_image(image), dev)
     if len(shape) != 3 or shape[2] != 3:
         raise KGLibraryError("predict_tiled: image must be uint8 [H, W, 3]")
     pl = plan(shape[0], shape[1], tile, overlap)
@@ -505,4 +510,8 @@ def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thres
     preds = []
     for a in range(0, len(pl), int(batch)):
         preds += inference.predict(model, x[a:a + int(batch)], nms_thresh, seg_thresh, None, max_workspace_bytes=max_workspace_bytes, packed=True)
-    return assemble(pl, preds, nms_thresh, dev, stage, clean)
+    out = assemble(pl, preds, nms_thresh, dev, stage, clean)
+    if measure:
+        from . import measure as _measure
+        out.measurements = _measure.measure_instances(out, image)
+    return out
