@@ -658,20 +658,27 @@ __global__ __launch_bounds__(1024) void wgrad_reduce_batch_kernel(const ReduceBa
 
 // the single-launch decomposition of one reduction: CH, threads per block, grid
 struct ReduceShape { int ch, nt, gx, gy; };
+static bool reduce_ch64(int Cout, int Cin) { return (long)Cout * ((Cin + 63) / 64) >= 2048; }
+// threads per block of the CH = 16 route.  1 tap with 16 <= nsplit < 32 gives 32 or 48: less than one wave, which the bias columns
+// (one WAVE per channel) cannot use -- kg_wgrad_reduce_bias refuses that combination
+static int reduce_nt16(int taps, int nsplit) {
+    int nt = 256;
+    const int E = taps * 16;
+    if (2 * E <= 1024 && nsplit >= 16) {       // few elements, many splits: several thread groups share the splits
+        int G = 1024 / E;
+        if (G > nsplit / 8) G = nsplit / 8;
+        if (G >= 2) nt = E * G;
+    }
+    return nt;
+}
 static ReduceShape reduce_shape(const ReduceDst& d, int Cout, int Cin, int taps, int nsplit) {
     ReduceShape r;
     // (bias partials: extra block columns after the Cout weight rows, one wave per channel)
-    if ((long)Cout * ((Cin + 63) / 64) >= 2048) {
+    if (reduce_ch64(Cout, Cin)) {
         r.ch = 64; r.nt = 256;
         r.gx = Cout + (d.bias_part ? (d.bias_C + 3) / 4 : 0); r.gy = (Cin + 63) / 64;
     } else {
-        int nt = 256;
-        const int E = taps * 16;
-        if (2 * E <= 1024 && nsplit >= 16) {       // few elements, many splits: several thread groups share the splits
-            int G = 1024 / E;
-            if (G > nsplit / 8) G = nsplit / 8;
-            if (G >= 2) nt = E * G;
-        }
+        const int nt = reduce_nt16(taps, nsplit);
         r.ch = 16; r.nt = nt;
         r.gx = Cout + (d.bias_part ? (d.bias_C + nt / 64 - 1) / (nt / 64) : 0); r.gy = (Cin + 15) / 16;
     }
@@ -765,6 +772,9 @@ extern "C" int kg_wgrad_reduce_bias(const float* part, float* const* grads, cons
         if (k < ngrads) { KG_CHECK_ARG(grads[k] && counts[k] > 0, "kg_wgrad_reduce_bias: bad tensor %d", k); end += counts[k]; }
         d.g[k] = grads[k < ngrads ? k : ngrads - 1]; d.end[k] = end;
     }
+    // (unreachable from kg_conv2d_wgrad_halo, whose bias partials come with 9 or 49 taps; reduce_shape would divide by nt / 64 = 0)
+    KG_CHECK_ARG(!bias_part || reduce_ch64(end, Cin) || reduce_nt16(KH * KW, nsplit) >= 64,
+                 "kg_wgrad_reduce_bias: bias partials with %d tap(s) and %d splits leave no whole wave per block", KH * KW, nsplit);
     d.bias_part = bias_part; d.db = db; d.bias_C = bias_C;
     return launch_reduce(part, d, end, Cin, KH * KW, nsplit, split_stride, accumulate, (hipStream_t)stream);
 }

@@ -301,6 +301,7 @@ def test_bilinear_forward_backward(shape):
 
 
 def test_detection_loss_matches_golden(golden):
+    """(per-element float64 parity on every index path of the loss kernels: tests/test_gpu_tail.py)"""
     from kg_instance_segmentation_amd.loss import DetectionLossAll
     g = golden("loss.npz")
     t = [torch.tensor(g[k], device=DEV, requires_grad=True) for k in ("kp", "short", "mid")]
@@ -315,6 +316,7 @@ def test_detection_loss_matches_golden(golden):
 
 
 def test_seg_loss_matches_golden(golden):
+    """(per-element float64 parity of kg_seg_loss over patch sizes, pair counts and 70 patches: tests/test_gpu_tail.py)"""
     from kg_instance_segmentation_amd.seg_loss import SEG_loss
     g = golden("loss.npz")
     patches = [[torch.tensor(g[f"seg.patch.{i}.{j}"], device=DEV, requires_grad=True) for j in range(n)] for i, n in ((0, 2), (1, 1))]
@@ -577,7 +579,8 @@ def test_conv_epilogue_bn_statistics(case):
 # ---- gradient scale of the half-precision backward pass (csrc/gradscale.hip, norm_pool.hip) --------------------------------------------
 def test_grad_scale_and_scale_tensors():
     """kg_grad_scale: S = the power of two that brings max |g| (kp maps: |g * p * (1 - p)|) into [2^(T-1), 2^T); zero / non-finite input ->
-    S = 1; kg_scale_tensors: per-tensor device scalars, exact for powers of two, sticky non-finite flag."""
+    S = 1; kg_scale_tensors: per-tensor device scalars, exact for powers of two, sticky non-finite flag.
+    (Every index path of both kernels, bit for bit: tests/test_gpu_tail.py.)"""
     T = ops.GRAD_TARGET_LOG2
     g = torch.Generator().manual_seed(0)
     a = (torch.randn(3, 5, 17, 19, generator=g) * 1e-6).to(DEV)
@@ -656,7 +659,8 @@ def test_rows_rescale_stage_boundary(dt):
 @pytest.mark.parametrize("case", [(2, 5, 16, 33, 37, True), (1, 10, 16, 40, 40, False), (3, 40, 48, 17, 19, False), (1, 64, 64, 16, 16, False), (1, 70, 72, 8, 8, False)])
 def test_grad_pack_matches_torch(case, dt):
     """kg_grad_pack (fp32 NCHW loss gradient -> rows planes, times p (1 - p) for sigmoid outputs, times the step's gradient scale): the LDS-transpose
-    kernel (cpad <= 64) and the per-pixel one (cpad > 64), pixel counts that are no multiple of the workgroup's 256."""
+    kernel (cpad <= 64) and the per-pixel one (cpad > 64), pixel counts that are no multiple of the workgroup's 256.
+    (Per element against float64, the 2048-block cap included: tests/test_gpu_tail.py.)"""
     N, C, cpad, H, W, with_prob = case
     g = torch.Generator().manual_seed(C + H)
     grad = torch.randn(N, C, H, W, generator=g).to(DEV)

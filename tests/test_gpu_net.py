@@ -323,7 +323,8 @@ def test_native_library_is_the_one_loaded():
 
 
 def test_fused_hip_adam_matches_torch_adam():
-    """kg_adam_step (one launch for all tensors) vs torch.optim.Adam over 3 steps incl. odd sizes, unaligned views and a changed lr."""
+    """kg_adam_step (one launch for all tensors) vs torch.optim.Adam over 3 steps incl. odd sizes, unaligned views and a changed lr.
+    (m, v and the update against float64 per job, weight decay, forced scalar paths, two bias corrections in one step: tests/test_gpu_tail.py.)"""
     from kg_instance_segmentation_amd.optim import Adam
     torch.manual_seed(5)
     shapes = [(64, 3, 7, 7), (5,), (1023,), (256, 64, 3, 3), (1,), (4097,)]
