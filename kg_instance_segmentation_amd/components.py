@@ -27,6 +27,7 @@ Semantics (include/kgnet_hip.h is the normative text)
 import numpy as np
 
 from . import _lib
+from ._labelmaps import device_maps, host_maps
 from .instances import Instances, TABLE_COLUMNS  # noqa: F401  (TABLE_COLUMNS: the columns of the tables returned here)
 
 KGLibraryError = _lib.KGLibraryError
@@ -42,10 +43,8 @@ def _conn(fn, connectivity, bg_connectivity):
 
 def _host_maps(fn, labels):
     """-> (int64 [nimg, H, W], was_2d)"""
-    lab = np.asarray(labels)
-    if lab.ndim not in (2, 3) or lab.dtype.kind not in "iu" or lab.size == 0:
-        raise KGLibraryError(f"{fn}: label maps must be a non-empty integer array [H, W] or [nimg, H, W]")
-    return lab.reshape((-1,) + lab.shape[-2:]).astype(np.int64), lab.ndim == 2
+    maps, single = host_maps(fn, labels, True)
+    return maps.astype(np.int64), single
 
 
 # ---- host statements of the semantics ---------------------------------------------------------------------------------------------------
@@ -247,26 +246,13 @@ def clean_host(labels, n, keep="largest", min_area=0, fill_holes=True, max_hole_
 
 # ---- device -----------------------------------------------------------------------------------------------------------------------------
 
-def _device_maps(fn, t, like=None):
-    import torch
-    if not torch.is_tensor(t) or t.device.type != "cuda":
-        raise KGLibraryError(f"{fn} (MI355X build) needs the label maps on a GPU device; the host route is {fn}_host")
-    if t.dtype != torch.int32 or t.dim() not in (2, 3) or t.numel() == 0:
-        raise KGLibraryError(f"{fn}: label maps must be a non-empty int32 tensor [H, W] or [nimg, H, W]")
-    if t.numel() > 2 ** 31 - 1:
-        raise KGLibraryError(f"{fn}: nimg * H * W exceeds 2^31 - 1")
-    if like is not None and (t.shape != like.shape or t.device != like.device):
-        raise KGLibraryError(f"{fn}: tensors of {tuple(t.shape)} and {tuple(like.shape)} must have one shape and one device")
-    return t.contiguous()
-
-
 def components(labels, connectivity=8, bg_connectivity=0):
     """labels: device int32 [H, W] or [nimg, H, W], any values -> (comp device int32 of the same shape, ncomp device int32 [nimg]).
     Six launches, no copy, no synchronisation (kg_label_components)."""
     import torch
     from ._lib import ptr, stream_ptr, c_long
     conn, bg = _conn("components", connectivity, bg_connectivity)
-    lab = _device_maps("components", labels)
+    lab = device_maps("components", labels, True)
     H, W = lab.shape[-2:]
     nimg = lab.numel() // (H * W)
     need = _lib.load().kg_label_components_workspace_bytes(nimg, H, W)
@@ -285,8 +271,8 @@ def component_stats(labels, comp, ncomp):
     (STATS_COLUMNS), comp_start host int32 [nimg + 1]).  Two device -> host copies: ncomp, then the stats."""
     import torch
     from ._lib import ptr, stream_ptr
-    lab = _device_maps("component_stats", labels)
-    cmp_ = _device_maps("component_stats", comp, lab)
+    lab = device_maps("component_stats", labels, True)
+    cmp_ = device_maps("component_stats", comp, True, lab)
     H, W = lab.shape[-2:]
     nimg = lab.numel() // (H * W)
     if not torch.is_tensor(ncomp) or ncomp.dtype != torch.int32 or tuple(ncomp.shape) != (nimg,):
@@ -308,7 +294,7 @@ def remap(comp, comp_start, newval):
     import torch
     from . import ops
     from ._lib import ptr, stream_ptr
-    cmp_ = _device_maps("remap", comp)
+    cmp_ = device_maps("remap", comp, True)
     H, W = cmp_.shape[-2:]
     nimg = cmp_.numel() // (H * W)
     cs = np.ascontiguousarray(np.asarray(comp_start, np.int64).reshape(-1).astype(np.int32))
@@ -337,7 +323,7 @@ def clean_batch(labels, ns, tables=None, **policy):
     import torch
     from . import tiling
     p = _policy("clean", policy)
-    lab = _device_maps("clean", labels)
+    lab = device_maps("clean", labels, True)
     if lab.dim() != 3 or len(ns) != lab.shape[0]:
         raise KGLibraryError("clean: a stack [nimg, H, W] and one instance count per image")
     nimg = lab.shape[0]
@@ -360,7 +346,7 @@ def clean(labels, n, keep="largest", min_area=0, fill_holes=True, max_hole_area=
     cost two device -> host copies (ncomp, then the stats); the refreshed table, which holds coordinate sums the stats do not, is one
     more.  ALL decisions are taken on the components of the INPUT map, in one pass (clean_host): call clean twice to fill the hole a
     dropped fragment leaves behind."""
-    lab = _device_maps("clean", labels)
+    lab = device_maps("clean", labels, True)
     if lab.dim() != 2:
         raise KGLibraryError("clean: one label map [H, W] (clean_batch takes a stack)")
     out, tabs, old = clean_batch(lab[None], [n], None if table is None else [table], keep=keep, min_area=min_area, fill_holes=fill_holes,

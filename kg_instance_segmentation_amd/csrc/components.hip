@@ -3,9 +3,8 @@
 //   kg_component_stats    per component {value, area, y1, x1, y2, x2, border, nb_min, nb_max}
 //   kg_component_remap    out = newval[component] (the host's decision written back into a label map)
 //
-// The rules of instances.hip / tiling.hip / labelmetrics.hip hold here too: every entry validates on the host before any HIP call and
-// never synchronises, the number of launches depends neither on the image content nor on the number of components, every output
-// element is written, integers only.  Plain C++ and vector memory operations only.
+// The rules of label_common.h hold here, with the exception its index rule names (below): the number of launches depends neither on the
+// image content nor on the number of components.
 //
 // Algorithm of kg_label_components: union-find whose root is the SMALLEST linear pixel index of a set.
 //   1. cc_tile_kernel     one workgroup per 64 x 64 tile resolves the tile in LDS (labels + parents, 32 KB): one wave owns a 64-pixel row, the
@@ -32,14 +31,10 @@
 //     fails it touches nothing (stats) / writes 0 (remap).
 // Because the root of a set is its smallest index whatever order the atomics land in, and the numbering is the raster order of the
 // roots, comp and ncomp do not depend on arrival order.  Label VALUES are only ever compared.
-#include "kg_common.h"
-#include <limits.h>
+#include "label_common.h"
 
-#define KG_CC_MAX_BLOCKS (1 << 20)      // grid cap: the kernels stride over what is left
-#define KG_CC_MAX_IMAGES 256            // images per stats / remap launch: their comp_start entries travel as a kernel argument
 #define KG_CC_STATS_BLOCKS 512         // grid of the stats walk: 2048 waves, each carrying one component from segment to segment
 #define KG_CC_BLOCK 4096                // pixels per block of the flatten / number / spread kernels (16 per thread)
-struct CcRanges { int start[KG_CC_MAX_IMAGES + 1]; };
 
 __device__ __forceinline__ int cc_conn(int v, int conn, int bg) { return v ? conn : bg; }
 // what a cell other workgroups update with atomics holds now (or held a moment ago)
@@ -201,7 +196,7 @@ __global__ __launch_bounds__(256) void cc_flatten_kernel(const int* __restrict__
             if (root == p) ++cnt;
             else atomicMin(par + p, root);
         }
-        for (int o = 32; o; o >>= 1) cnt += __shfl_xor(cnt, o);
+        cnt = kg_wave_sum(cnt);
         if (lane == 0) part[wave] = cnt;
         __syncthreads();
         if (threadIdx.x == 0) blocksum[b] = part[0] + part[1] + part[2] + part[3];
@@ -311,16 +306,15 @@ __device__ __forceinline__ void cc_stats_commit(int* st, int v, int area, int y1
     if (hi > cc_peek(st + 8)) atomicMax(st + 8, hi);
 }
 
-// label_stats_kernel's walk over the images of one launch: one wave per 64-pixel segment of a row, the grid striding over the segments; a
-// lane is a run head when its comp value differs from the pixel to its left in the segment (or it is the segment's first lane).  Every
-// lane looks at its four neighbours in the image; the smallest and largest neighbouring value that differs from the lane's own are
+// The run walk of kg_seg_run over the comp values of the images of one launch: one wave per 64-pixel segment of a row, the grid
+// striding over the segments.  Every lane looks at its four neighbours in the image; the smallest and largest neighbouring value that differs from the lane's own are
 // reduced over the lanes of the run by shuffles, and the head issues the run's integer atomics (max, add, min, max, or): arrival order
 // cannot change the result.  The row index c - 1 is formed only inside (unsigned)(c - 1) < (unsigned)m.
 // One component can own most segments (the background: measured, its runs' adds to ONE address were 3/4 of the kernel), so every wave
 // carries ONE component along in wave-uniform registers -- the first valid one of a segment, replaced when a segment does not hold it --
 // folds the pixels of that component into them by ballots instead of atomics, and commits them when it lets go: the same integers by
 // the same associative operations.
-__global__ __launch_bounds__(256) void cc_stats_kernel(const int* __restrict__ labels, const int* __restrict__ comp, int cnt, int H, int W, CcRanges rg,
+__global__ __launch_bounds__(256) void cc_stats_kernel(const int* __restrict__ labels, const int* __restrict__ comp, int cnt, int H, int W, KgRanges rg,
                                                        int* __restrict__ stats) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long spr = (W + 63) >> 6, spi = (long)H * spr, nseg = spi * cnt, HW = (long)H * W;
@@ -329,19 +323,13 @@ __global__ __launch_bounds__(256) void cc_stats_kernel(const int* __restrict__ l
     for (long s = (long)blockIdx.x * 4 + wave; s < nseg; s += (long)gridDim.x * 4) {
         const int img = (int)(s / spi);
         const long si = s - (long)img * spi;
-        const int y = (int)(si / spr), x0 = (int)(si - (long)y * spr) << 6, x = x0 + lane;
         const int row0 = rg.start[img], m = rg.start[img + 1] - row0;
-        const bool live = x < W;
-        const long idx = (long)img * HW + (long)y * W + x;
-        const int c = live ? comp[idx] : 0;
-        const int left = __shfl_up(c, 1);
-        const bool valid = live && (unsigned)c - 1u < (unsigned)m;
+        const KgSegRun r = kg_seg_run(si, spr, W, comp + (long)img * HW);
+        const int y = r.y, x = r.x, x0 = x - lane, c = r.v, end = r.end;
+        const bool head = r.head;
+        const long idx = (long)img * HW + r.p;
+        const bool valid = r.live && (unsigned)c - 1u < (unsigned)m;
         const int row = valid ? row0 + (int)((unsigned)c - 1u) : -1;               // < total: the only index made from c
-        const bool head = live && (lane == 0 || c != left);
-        const unsigned long long heads = __ballot(head);
-        const int nlive = __popcll(__ballot(live));
-        const unsigned long long later = lane == 63 ? 0ull : heads & ~((2ull << lane) - 1ull);
-        const int end = later ? __builtin_ctzll(later) : nlive;                    // one past the last lane of this lane's run
         int lo = INT_MAX, hi = INT_MIN;
         if (valid) {
             int nb[4];
@@ -401,7 +389,7 @@ __global__ __launch_bounds__(256) void cc_stats_finish_kernel(int* __restrict__ 
 
 // ---- remap -------------------------------------------------------------------------------------------------------------------------------
 // blockIdx.y = image of the launch; out = newval[comp_start[i] + c - 1] inside (unsigned)(c - 1) < (unsigned)m_i, else 0
-__global__ __launch_bounds__(256) void cc_remap_kernel(const int* __restrict__ comp, int H, int W, CcRanges rg, const int* __restrict__ newval,
+__global__ __launch_bounds__(256) void cc_remap_kernel(const int* __restrict__ comp, int H, int W, KgRanges rg, const int* __restrict__ newval,
                                                        int* __restrict__ out) {
     const int img = blockIdx.y;
     const int row0 = rg.start[img], m = rg.start[img + 1] - row0;
@@ -413,29 +401,18 @@ __global__ __launch_bounds__(256) void cc_remap_kernel(const int* __restrict__ c
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------------------
-static inline bool cc_aligned(const void* p) { return ((unsigned long long)(size_t)p & 3ull) == 0; }
 static inline long cc_nbi(int H, int W) { return ((long)H * W + KG_CC_BLOCK - 1) / KG_CC_BLOCK; }
-static inline unsigned cc_grid(long blocks) { return (unsigned)(blocks < 1 ? 1 : blocks < KG_CC_MAX_BLOCKS ? blocks : KG_CC_MAX_BLOCKS); }
+static inline unsigned cc_grid(long blocks) { return kg_grid_cap(blocks < 1 ? 1 : blocks); }
 
 static int cc_check_size(const char* fn, int nimg, int H, int W) {
     KG_CHECK_ARG(nimg > 0 && H > 0 && W > 0, "%s: bad size (nimg %d, H %d, W %d)", fn, nimg, H, W);
-    KG_CHECK_ARG((long)H * W <= 0x7fffffffL && (long)H * W * nimg <= 0x7fffffffL, "%s: nimg * H * W exceeds 2^31 - 1", fn);
-    return KG_OK;
+    return kg_check_stack_size(fn, nimg, H, W);
 }
 
 static int cc_check_start(const char* fn, const int* comp_start, int nimg, int total) {
     KG_CHECK_ARG(comp_start, "%s: null pointer (comp_start)", fn);
     KG_CHECK_ARG(total >= 0 && (long)total * 9 <= 0x7fffffffL, "%s: bad total %d", fn, total);
-    KG_CHECK_ARG(comp_start[0] == 0, "%s: comp_start[0] is %d, not 0", fn, comp_start[0]);
-    for (int i = 0; i < nimg; ++i)
-        KG_CHECK_ARG(comp_start[i + 1] >= comp_start[i], "%s: comp_start decreases at image %d", fn, i);
-    KG_CHECK_ARG(comp_start[nimg] == total, "%s: comp_start[nimg] is %d, not total = %d", fn, comp_start[nimg], total);
-    return KG_OK;
-}
-
-static void cc_ranges(const int* comp_start, int i0, int cnt, CcRanges* rg) {
-    for (int i = 0; i <= cnt; ++i) rg->start[i] = comp_start[i0 + i];
-    for (int i = cnt + 1; i <= KG_CC_MAX_IMAGES; ++i) rg->start[i] = comp_start[i0 + cnt];
+    return kg_check_start(fn, "comp_start", comp_start, nimg, total, "total");
 }
 
 // parents (one int per pixel) followed by the block counts (one int per 4096-pixel block of every image)
@@ -446,13 +423,12 @@ extern "C" long kg_label_components_workspace_bytes(int nimg, int H, int W) {
 
 extern "C" int kg_label_components(const int* labels, int nimg, int H, int W, int connectivity, int bg_connectivity, int* comp, int* ncomp,
                                    void* workspace, long workspace_bytes, void* stream) {
-    const int rc = cc_check_size("kg_label_components", nimg, H, W);
-    if (rc != KG_OK) return rc;
+    KG_TRY(cc_check_size("kg_label_components", nimg, H, W));
     KG_CHECK_ARG(connectivity == 4 || connectivity == 8, "kg_label_components: connectivity %d is not 4 or 8", connectivity);
     KG_CHECK_ARG(bg_connectivity == 0 || bg_connectivity == 4 || bg_connectivity == 8, "kg_label_components: bg_connectivity %d is not 0, 4 or 8",
                  bg_connectivity);
     KG_CHECK_ARG(labels && comp && ncomp && workspace, "kg_label_components: null pointer (labels / comp / ncomp / workspace)");
-    KG_CHECK_ARG(cc_aligned(labels) && cc_aligned(comp) && cc_aligned(ncomp) && cc_aligned(workspace), "kg_label_components: misaligned pointer");
+    KG_CHECK_ARG(kg_aligned(labels, 3) && kg_aligned(comp, 3) && kg_aligned(ncomp, 3) && kg_aligned(workspace, 3), "kg_label_components: misaligned pointer");
     KG_CHECK_ARG(labels != comp, "kg_label_components: comp aliases labels");
     const long need = kg_label_components_workspace_bytes(nimg, H, W);
     KG_CHECK_ARG(workspace_bytes >= need, "kg_label_components: workspace of %ld bytes, %ld needed", workspace_bytes, need);
@@ -484,21 +460,19 @@ extern "C" int kg_label_components(const int* labels, int nimg, int H, int W, in
 
 extern "C" int kg_component_stats(const int* labels, const int* comp, int nimg, int H, int W, const int* comp_start, int total, int* stats,
                                   void* stream) {
-    int rc = cc_check_size("kg_component_stats", nimg, H, W);
-    if (rc != KG_OK) return rc;
-    rc = cc_check_start("kg_component_stats", comp_start, nimg, total);
-    if (rc != KG_OK) return rc;
+    KG_TRY(cc_check_size("kg_component_stats", nimg, H, W));
+    KG_TRY(cc_check_start("kg_component_stats", comp_start, nimg, total));
     KG_CHECK_ARG(labels && comp, "kg_component_stats: null pointer (labels / comp)");
     KG_CHECK_ARG(stats || total == 0, "kg_component_stats: null pointer (stats)");
-    KG_CHECK_ARG(cc_aligned(labels) && cc_aligned(comp) && cc_aligned(stats), "kg_component_stats: misaligned pointer");
+    KG_CHECK_ARG(kg_aligned(labels, 3) && kg_aligned(comp, 3) && kg_aligned(stats, 3), "kg_component_stats: misaligned pointer");
     const long HW = (long)H * W, cells = (long)total * 9;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(cc_stats_init_kernel, dim3((unsigned)(cells ? kg_cdiv(cells, 256) : 1)), dim3(256), 0, st, stats, total);
     KG_CHECK_LAUNCH("component_stats_init");
-    for (int i0 = 0; i0 < nimg; i0 += KG_CC_MAX_IMAGES) {
-        const int cnt = nimg - i0 < KG_CC_MAX_IMAGES ? nimg - i0 : KG_CC_MAX_IMAGES;
-        CcRanges rg;
-        cc_ranges(comp_start, i0, cnt, &rg);
+    for (int i0 = 0; i0 < nimg; i0 += KG_MAX_IMAGES) {
+        const int cnt = nimg - i0 < KG_MAX_IMAGES ? nimg - i0 : KG_MAX_IMAGES;
+        KgRanges rg;
+        kg_ranges(comp_start, i0, cnt, &rg);
         const long nseg = (long)H * ((W + 63) / 64) * cnt, nb = (nseg + 3) / 4;
         hipLaunchKernelGGL(cc_stats_kernel, dim3((unsigned)(nb < KG_CC_STATS_BLOCKS ? nb : KG_CC_STATS_BLOCKS)), dim3(256), 0, st, labels + HW * i0, comp + HW * i0, cnt, H, W, rg, stats);
         KG_CHECK_LAUNCH("component_stats");
@@ -510,19 +484,17 @@ extern "C" int kg_component_stats(const int* labels, const int* comp, int nimg, 
 
 extern "C" int kg_component_remap(const int* comp, int nimg, int H, int W, const int* comp_start, int total, const int* newval, int* out,
                                   void* stream) {
-    int rc = cc_check_size("kg_component_remap", nimg, H, W);
-    if (rc != KG_OK) return rc;
-    rc = cc_check_start("kg_component_remap", comp_start, nimg, total);
-    if (rc != KG_OK) return rc;
+    KG_TRY(cc_check_size("kg_component_remap", nimg, H, W));
+    KG_TRY(cc_check_start("kg_component_remap", comp_start, nimg, total));
     KG_CHECK_ARG(comp && out, "kg_component_remap: null pointer (comp / out)");
     KG_CHECK_ARG(newval || total == 0, "kg_component_remap: null pointer (newval)");
-    KG_CHECK_ARG(cc_aligned(comp) && cc_aligned(newval) && cc_aligned(out), "kg_component_remap: misaligned pointer");
+    KG_CHECK_ARG(kg_aligned(comp, 3) && kg_aligned(newval, 3) && kg_aligned(out, 3), "kg_component_remap: misaligned pointer");
     KG_CHECK_ARG(out != comp && (out != newval || total == 0), "kg_component_remap: out aliases an input");
     const long HW = (long)H * W;
-    for (int i0 = 0; i0 < nimg; i0 += KG_CC_MAX_IMAGES) {
-        const int cnt = nimg - i0 < KG_CC_MAX_IMAGES ? nimg - i0 : KG_CC_MAX_IMAGES;
-        CcRanges rg;
-        cc_ranges(comp_start, i0, cnt, &rg);
+    for (int i0 = 0; i0 < nimg; i0 += KG_MAX_IMAGES) {
+        const int cnt = nimg - i0 < KG_MAX_IMAGES ? nimg - i0 : KG_MAX_IMAGES;
+        KgRanges rg;
+        kg_ranges(comp_start, i0, cnt, &rg);
         const long nb = (HW + 255) / 256;
         hipLaunchKernelGGL(cc_remap_kernel, dim3((unsigned)(nb < 65536 ? nb : 65536), (unsigned)cnt), dim3(256), 0, (hipStream_t)stream, comp + HW * i0, H, W, rg,
                            newval, out + HW * i0);

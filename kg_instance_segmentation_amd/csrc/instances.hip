@@ -3,7 +3,7 @@
 // Input = the masks of one or more images of one size in the bit-mask layout of include/kgnet_hip.h, all rows concatenated; image i owns
 // rows [row_start[i], row_start[i + 1]).  Row order is priority order (predict's rows are sorted by descending confidence).
 //
-// Every output has a size the host knows, and no address in a kernel depends on a value read from device memory: addresses come from the
+// The index rule of label_common.h holds without exception here: every output has a size the host knows, and addresses come from the
 // grid indices, the loop counters and the host-validated row ranges (passed by value) alone.  Values read from words / ids / colors only
 // ever become predicates or stored values.
 //
@@ -13,12 +13,9 @@
 // them is broadcast with v_readlane for every lane to test its own bit.  The label kernel leaves a position once every live lane is
 // resolved; the overlay visits every covering row, in ascending order, because the blend compounds.
 // Compiled with -ffp-contract=off: the overlay's float64 expression must round product by product, as NumPy evaluates it.
-#include "kg_common.h"
-#include <limits.h>
+#include "label_common.h"
 
-#define KG_INST_MAX_IMAGES 256      // images per launch: their row ranges travel by value in the kernel arguments
 #define KG_INST_WPW 8               // consecutive words a wave walks (one 64-byte line of every row it gathers from)
-struct InstRanges { int start[KG_INST_MAX_IMAGES + 1]; };
 
 // lane j's value for every lane; j is wave-uniform (it comes from a ballot)
 __device__ __forceinline__ unsigned inst_lane_u32(unsigned v, int j) { return (unsigned)__builtin_amdgcn_readlane((int)v, j); }
@@ -30,7 +27,7 @@ __device__ __forceinline__ double inst_lane_f64(double v, int j) { return __long
 
 // labels[img][y][x] = id of the first row of the image, in row order, whose bit is set; 0 if none.  id = ids[row] (a value, never an
 // index) or row - row_start[img] + 1.
-__global__ __launch_bounds__(256) void instance_labels_kernel(const unsigned long long* __restrict__ words, long ld_words, const InstRanges rg, int H,
+__global__ __launch_bounds__(256) void instance_labels_kernel(const unsigned long long* __restrict__ words, long ld_words, const KgRanges rg, int H,
                                                               int W, const int* __restrict__ ids, int* __restrict__ labels) {
     const int lane = threadIdx.x & 63, wpr = (W + 63) >> 6, img = blockIdx.y;
     const long nw = (long)H * wpr;
@@ -71,24 +68,12 @@ __device__ __forceinline__ int inst_bitpos_sum(unsigned long long w) {
            (__builtin_popcountll(w & 0xF0F0F0F0F0F0F0F0ull) << 2) + (__builtin_popcountll(w & 0xFF00FF00FF00FF00ull) << 3) +
            (__builtin_popcountll(w & 0xFFFF0000FFFF0000ull) << 4) + (__builtin_popcountll(w & 0xFFFFFFFF00000000ull) << 5);
 }
-__device__ __forceinline__ long long inst_wave_sum(long long v) {
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ int inst_wave_min(int v) {
-    for (int o = 32; o; o >>= 1) { const int t = __shfl_xor(v, o); v = t < v ? t : v; }
-    return v;
-}
-__device__ __forceinline__ int inst_wave_max(int v) {
-    for (int o = 32; o; o >>= 1) { const int t = __shfl_xor(v, o); v = t > v ? t : v; }
-    return v;
-}
 
 // table[row] = {area_full, area_visible, y1, x1, y2, x2, sum_y, sum_x}.  One block per row; lane l of a wave owns word k0 + l of the row
 // (coalesced), and the pixels the row wins are its own bits minus those of the earlier rows of its image at the same word -- the label
 // map's rule, recomputed from the words, so that ids need not be distinct.  A lane whose word has nothing left loads nothing more, and a
 // wave leaves the earlier rows once no lane has anything left.  Integers only: no atomics, no initialisation, any order gives the same table.
-__global__ __launch_bounds__(256) void instance_table_kernel(const unsigned long long* __restrict__ words, long ld_words, const InstRanges rg, int H,
+__global__ __launch_bounds__(256) void instance_table_kernel(const unsigned long long* __restrict__ words, long ld_words, const KgRanges rg, int H,
                                                              int W, long long* __restrict__ table) {
     __shared__ long long part[4][8];
     const int img = blockIdx.y, rs = rg.start[img], re = rg.start[img + 1];
@@ -129,13 +114,15 @@ __global__ __launch_bounds__(256) void instance_table_kernel(const unsigned long
             x2 = xr > x2 ? xr : x2;
         }
     }
-    area_full = inst_wave_sum(area_full); area = inst_wave_sum(area); sum_y = inst_wave_sum(sum_y); sum_x = inst_wave_sum(sum_x);
-    y1 = inst_wave_min(y1); x1 = inst_wave_min(x1); y2 = inst_wave_max(y2); x2 = inst_wave_max(x2);
+    area_full = kg_wave_sum(area_full); area = kg_wave_sum(area); sum_y = kg_wave_sum(sum_y); sum_x = kg_wave_sum(sum_x);
+    y1 = kg_wave_min(y1); x1 = kg_wave_min(x1); y2 = kg_wave_max(y2); x2 = kg_wave_max(x2);
     if (lane == 0) {
         long long* p = part[wave];
         p[0] = area_full; p[1] = area; p[2] = y1; p[3] = x1; p[4] = y2; p[5] = x2; p[6] = sum_y; p[7] = sum_x;
     }
     __syncthreads();
+    // kg_block_combine (label_common.h), kept as this kernel's own copy: with the shared function the label-map-and-table leg at
+    // 512^2, N = 8 measured above the parent's maximum twice (profiles/labelcommon_ab.json)
     if (threadIdx.x < 8) {
         const int c = threadIdx.x;
         long long v = part[0][c];
@@ -155,7 +142,7 @@ __global__ __launch_bounds__(256) void instance_table_kernel(const unsigned long
 // v = (uint8)(v * (1 - alpha) + alpha * color[c] * 255), float64, products and sums in exactly that order, truncated as NumPy's assignment
 // into a uint8 image does (float64 -> integer -> low byte).  image and out may be the same buffer: a lane reads and writes its own pixel only.
 __global__ __launch_bounds__(256) void instance_overlay_kernel(const unsigned char* image, const unsigned long long* __restrict__ words, long ld_words,
-                                                               const InstRanges rg, int H, int W, const double* __restrict__ colors, double alpha,
+                                                               const KgRanges rg, int H, int W, const double* __restrict__ colors, double alpha,
                                                                unsigned char* out) {
     const int lane = threadIdx.x & 63, wpr = (W + 63) >> 6, img = blockIdx.y;
     const long nw = (long)H * wpr;
@@ -199,15 +186,11 @@ __global__ __launch_bounds__(256) void instance_overlay_kernel(const unsigned ch
 static int inst_check(const char* fn, const void* words, long ld_words, int n, const int* row_start, int nimg, int H, int W) {
     KG_CHECK_ARG(row_start, "%s: null pointer (row_start)", fn);
     KG_CHECK_ARG(H > 0 && W > 0 && n >= 0 && nimg > 0, "%s: bad size (H %d, W %d, n %d, nimg %d)", fn, H, W, n, nimg);
-    const long wpr = (W + 63) / 64, need = ((long)H * wpr + 1) & ~1L;
-    KG_CHECK_ARG(ld_words % 2 == 0 && ld_words >= need && ld_words <= 0x7fffffffL, "%s: ld_words %ld too small or odd (need %ld)", fn, ld_words, need);
+    KG_TRY(kg_check_bits_ld(fn, H, W, ld_words));
     KG_CHECK_ARG(words || n == 0, "%s: null pointer (words)", fn);
-    KG_CHECK_ARG(((unsigned long long)(size_t)words & 15) == 0, "%s: words must be 16-byte aligned", fn);
-    KG_CHECK_ARG(row_start[0] == 0, "%s: row_start[0] is %d, not 0", fn, row_start[0]);
-    for (int i = 0; i < nimg; ++i)
-        KG_CHECK_ARG(row_start[i + 1] >= row_start[i], "%s: row_start decreases at image %d", fn, i);
-    KG_CHECK_ARG(row_start[nimg] == n, "%s: row_start[nimg] is %d, not n = %d", fn, row_start[nimg], n);
-    KG_CHECK_ARG((long)nimg * H * W <= 0x7fffffffL, "%s: nimg * H * W exceeds 2^31 - 1", fn);
+    KG_CHECK_ARG(kg_aligned(words, 15), "%s: words must be 16-byte aligned", fn);
+    KG_TRY(kg_check_start(fn, "row_start", row_start, nimg, n, "n"));
+    KG_TRY(kg_check_stack_size(fn, nimg, H, W));
     KG_CHECK_ARG((long)n <= LONG_MAX / 8 / ld_words, "%s: n * ld_words too large", fn);
     return KG_OK;
 }
@@ -215,26 +198,17 @@ static inline dim3 inst_grid(int H, int W, int nimg) {
     const long nw = (long)H * ((W + 63) / 64);
     return dim3((unsigned)((nw + 4 * KG_INST_WPW - 1) / (4 * KG_INST_WPW)), (unsigned)nimg);
 }
-// the ranges of images [i0, i0 + cnt) (absolute rows); returns the largest row count among them
-static int inst_ranges(const int* row_start, int i0, int cnt, InstRanges* rg) {
-    int most = 0;
-    for (int i = 0; i <= cnt; ++i) rg->start[i] = row_start[i0 + i];
-    for (int i = cnt + 1; i <= KG_INST_MAX_IMAGES; ++i) rg->start[i] = row_start[i0 + cnt];
-    for (int i = 0; i < cnt; ++i) most = rg->start[i + 1] - rg->start[i] > most ? rg->start[i + 1] - rg->start[i] : most;
-    return most;
-}
 
 // words: device [n][ld_words]; row_start: HOST int [nimg + 1]; ids: device int [n] or NULL; labels: device int [nimg][H][W];
 // table: device int64 [n][8] or NULL.  One launch for the label map and one for the table per 256 images; no host synchronisation.
 extern "C" int kg_instance_labels(const void* words, long ld_words, int n, const int* row_start, int nimg, int H, int W, const int* ids, int* labels,
                                   long long* table, void* stream) {
-    const int rc = inst_check("kg_instance_labels", words, ld_words, n, row_start, nimg, H, W);
-    if (rc != KG_OK) return rc;
+    KG_TRY(inst_check("kg_instance_labels", words, ld_words, n, row_start, nimg, H, W));
     KG_CHECK_ARG(labels, "kg_instance_labels: null pointer (labels)");
-    for (int i0 = 0; i0 < nimg; i0 += KG_INST_MAX_IMAGES) {
-        const int cnt = nimg - i0 < KG_INST_MAX_IMAGES ? nimg - i0 : KG_INST_MAX_IMAGES;
-        InstRanges rg;
-        const int most = inst_ranges(row_start, i0, cnt, &rg);
+    for (int i0 = 0; i0 < nimg; i0 += KG_MAX_IMAGES) {
+        const int cnt = nimg - i0 < KG_MAX_IMAGES ? nimg - i0 : KG_MAX_IMAGES;
+        KgRanges rg;
+        const int most = kg_ranges(row_start, i0, cnt, &rg);
         hipLaunchKernelGGL(instance_labels_kernel, inst_grid(H, W, cnt), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)words, ld_words,
                            rg, H, W, ids, labels + (long)i0 * H * W);
         KG_CHECK_LAUNCH("instance_labels");
@@ -250,14 +224,13 @@ extern "C" int kg_instance_labels(const void* words, long ld_words, int n, const
 // image / out: device bytes [nimg][H][W][3] (out may equal image); colors: device float64 [n][3]; one launch per 256 images
 extern "C" int kg_instance_overlay(const void* image, const void* words, long ld_words, int n, const int* row_start, int nimg, int H, int W,
                                    const double* colors, double alpha, void* out, void* stream) {
-    const int rc = inst_check("kg_instance_overlay", words, ld_words, n, row_start, nimg, H, W);
-    if (rc != KG_OK) return rc;
+    KG_TRY(inst_check("kg_instance_overlay", words, ld_words, n, row_start, nimg, H, W));
     KG_CHECK_ARG(image && out && (colors || n == 0), "kg_instance_overlay: null pointer");
     KG_CHECK_ARG(alpha >= 0 && alpha <= 1, "kg_instance_overlay: alpha %g outside [0, 1]", alpha);
-    for (int i0 = 0; i0 < nimg; i0 += KG_INST_MAX_IMAGES) {
-        const int cnt = nimg - i0 < KG_INST_MAX_IMAGES ? nimg - i0 : KG_INST_MAX_IMAGES;
-        InstRanges rg;
-        inst_ranges(row_start, i0, cnt, &rg);
+    for (int i0 = 0; i0 < nimg; i0 += KG_MAX_IMAGES) {
+        const int cnt = nimg - i0 < KG_MAX_IMAGES ? nimg - i0 : KG_MAX_IMAGES;
+        KgRanges rg;
+        kg_ranges(row_start, i0, cnt, &rg);
         const long off = (long)i0 * H * W * 3;
         hipLaunchKernelGGL(instance_overlay_kernel, inst_grid(H, W, cnt), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)image + off,
                            (const unsigned long long*)words, ld_words, rg, H, W, colors, alpha, (unsigned char*)out + off);

@@ -4,45 +4,25 @@
 //                     sums, the 4-neighbour edge counts (all, frame, contact, boundary pixels) and per image channel sum, sum of squares,
 //                     min and max
 //
-// The rules of instances.hip / tiling.hip / labelmetrics.hip hold here too: the entry validates on the host before any HIP call and never
-// synchronises, the number of launches does not depend on m, every output element is written, integers only.
-//
-// INDEX RULE.  No value read from device memory becomes an index.  The job table is the one device-read table: its box is clamped to
-// the map before any address is formed, and its image index is used only inside the predicate (unsigned)img < (unsigned)nimg (a job
-// that fails it writes a row of zeros and reads nothing else).  Labels and pixel values are predicates and summands only.  A neighbour
-// outside the map is decided by a predicate on its coordinates before its address exists.
-// Plain C++ and vector memory operations only, no atomics.
-#include "kg_common.h"
-#include <limits.h>
+// The index rule of label_common.h holds here.  The job table is the one device-read table: its box is clamped to the map before any
+// address is formed, and its image index is used only inside the predicate (unsigned)img < (unsigned)nimg (a job that fails it writes a
+// row of zeros and reads nothing else).  A neighbour outside the map is decided by a predicate on its coordinates before its address
+// exists.  No atomics.
+#include "label_common.h"
 
-#define KG_MS_MAX_BLOCKS (1 << 20)      // grid cap: the blocks stride over what is left
 #define KG_MS_MAX_SIDE 32768            // H, W <= 2^15: area <= 2^30, a coordinate product < 2^30, a coordinate sum < 2^60, and a uint16
                                         // sum of squares < 2^62 -- every column fits int64 and nothing else needs checking
 #define KG_MS_GEOM 10                   // geometry columns; 4 more per channel
 #define KG_MS_MAX_COLS (KG_MS_GEOM + 4 * 4)
 
-__device__ __forceinline__ long long ms_wave_sum(long long v) {
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ int ms_wave_sum(int v) {
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ int ms_wave_min(int v) {
-    for (int o = 32; o; o >>= 1) { const int t = __shfl_xor(v, o); v = t < v ? t : v; }
-    return v;
-}
-__device__ __forceinline__ int ms_wave_max(int v) {
-    for (int o = 32; o; o >>= 1) { const int t = __shfl_xor(v, o); v = t > v ? t : v; }
-    return v;
-}
-
-// One block per job (the grid strides when there are more jobs than KG_MS_MAX_BLOCKS): label_table_kernel's walk -- the clamped box as
-// one flat row-major list, thread t takes elements t, t + 256, ..., the position advances by additions -- so consecutive lanes read
-// consecutive pixels of a box row.  A lane whose pixel holds the id reads its four neighbours FROM THE MAP (a box or band edge inside the
-// map is not an object edge), each under a coordinate predicate, and the pixel's C channel values.  Partials are reduced by shuffles
-// and 4 * (10 + 4 C) * 8 bytes of LDS.
+// One block per job (the grid strides when there are more jobs than KG_LABEL_MAX_BLOCKS), walking its clamped box.  A lane whose pixel
+// holds the id reads its four neighbours FROM THE MAP (a box or band edge inside the map is not an object edge), each under a
+// coordinate predicate, and the pixel's C channel values.  Partials are reduced by shuffles and 4 * (10 + 4 C) * 8 bytes of LDS.
+//
+// This kernel keeps ITS OWN COPY of the clamped box, of the walk (kg_job_box / kg_box_walk of label_common.h state the rule: the same
+// clamp, the same flat row-major list, additions only) and of the four-wave combine: written with the shared functions its 3-channel
+// leg measured 10-25 % slower than with this text, twice (profiles/labelcommon_ab.json).  A change to the walk or the clamp in
+// label_common.h is made here too.
 //
 // 32-bit partials, with their bound: a box holds at most 2^30 pixels, so a thread visits at most 2^22 of them and a wave 2^28; the five
 // counts (area, the three edge counts, boundary pixels) add at most 4 per visited pixel, so a thread's count stays below 2^24 and a
@@ -98,13 +78,13 @@ __global__ __launch_bounds__(256) void label_measure_kernel(const int* __restric
                 if (xx >= bw) { xx -= bw; ++yy; }
             }
         }
-        area = ms_wave_sum(area); edges = ms_wave_sum(edges); e_border = ms_wave_sum(e_border); e_contact = ms_wave_sum(e_contact);
-        bpix = ms_wave_sum(bpix);
-        sy = ms_wave_sum(sy); sx = ms_wave_sum(sx); syy = ms_wave_sum(syy); syx = ms_wave_sum(syx); sxx = ms_wave_sum(sxx);
+        area = kg_wave_sum(area); edges = kg_wave_sum(edges); e_border = kg_wave_sum(e_border); e_contact = kg_wave_sum(e_contact);
+        bpix = kg_wave_sum(bpix);
+        sy = kg_wave_sum(sy); sx = kg_wave_sum(sx); syy = kg_wave_sum(syy); syx = kg_wave_sum(syx); sxx = kg_wave_sum(sxx);
         if constexpr (C > 0) {
 #pragma unroll
             for (int c = 0; c < C; ++c) {
-                vsum[c] = ms_wave_sum(vsum[c]); vsq[c] = ms_wave_sum(vsq[c]); vmin[c] = ms_wave_min(vmin[c]); vmax[c] = ms_wave_max(vmax[c]);
+                vsum[c] = kg_wave_sum(vsum[c]); vsq[c] = kg_wave_sum(vsq[c]); vmin[c] = kg_wave_min(vmin[c]); vmax[c] = kg_wave_max(vmax[c]);
             }
         }
         if (lane == 0) {
@@ -138,11 +118,9 @@ __global__ __launch_bounds__(256) void label_measure_kernel(const int* __restric
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------
-static inline bool ms_aligned(const void* p, unsigned mask) { return ((unsigned long long)(size_t)p & mask) == 0; }
-
 template <int C, typename T>
 static void ms_launch(const int* labels, int nimg, int H, int W, const void* image, const int* jobs, int m, long long* out, hipStream_t stream) {
-    hipLaunchKernelGGL((label_measure_kernel<C, T>), dim3((unsigned)(m < KG_MS_MAX_BLOCKS ? m : KG_MS_MAX_BLOCKS)), dim3(256), 0, stream, labels, nimg, H, W,
+    hipLaunchKernelGGL((label_measure_kernel<C, T>), dim3(kg_grid_cap(m)), dim3(256), 0, stream, labels, nimg, H, W,
                        (const T*)image, jobs, m, out);
 }
 
@@ -153,13 +131,13 @@ extern "C" int kg_label_measure(const int* labels, int nimg, int H, int W, const
     KG_CHECK_ARG(nimg > 0 && H > 0 && W > 0 && m >= 0, "kg_label_measure: bad size (nimg %d, H %d, W %d, m %d)", nimg, H, W, m);
     KG_CHECK_ARG(H <= KG_MS_MAX_SIDE && W <= KG_MS_MAX_SIDE, "kg_label_measure: H %d, W %d exceed %d (the bound that keeps every sum inside int64)", H, W,
                  KG_MS_MAX_SIDE);
-    KG_CHECK_ARG((long)nimg * H * W <= 0x7fffffffL, "kg_label_measure: nimg * H * W exceeds 2^31 - 1");
+    KG_TRY(kg_check_stack_size("kg_label_measure", nimg, H, W));
     KG_CHECK_ARG(channels >= 0 && channels <= 4, "kg_label_measure: channels %d (0 .. 4)", channels);
     KG_CHECK_ARG(elem_bytes == 1 || elem_bytes == 2, "kg_label_measure: elem_bytes %d (1 or 2)", elem_bytes);
     KG_CHECK_ARG(labels, "kg_label_measure: null pointer (labels)");
     KG_CHECK_ARG((image != nullptr) == (channels > 0), "kg_label_measure: image must be NULL exactly when channels == 0 (channels %d)", channels);
     KG_CHECK_ARG((jobs && out) || m == 0, "kg_label_measure: null pointer (jobs / out)");
-    KG_CHECK_ARG(ms_aligned(labels, 3) && ms_aligned(jobs, 3) && ms_aligned(out, 7) && ms_aligned(image, elem_bytes == 2 ? 1 : 0),
+    KG_CHECK_ARG(kg_aligned(labels, 3) && kg_aligned(jobs, 3) && kg_aligned(out, 7) && kg_aligned(image, elem_bytes == 2 ? 1 : 0),
                  "kg_label_measure: misaligned pointer");
     if (m == 0) return KG_OK;
     hipStream_t s = (hipStream_t)stream;

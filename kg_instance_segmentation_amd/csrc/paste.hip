@@ -6,7 +6,7 @@
 // Interpolation rule = the published generic INTER_LINEAR float path of OpenCV's resize.cpp (oracle/paste.py states it and why
 // it is "parity unpinned": cv2 is absent here); compiled with -ffp-contract=off so that every product and sum rounds as written
 // (horizontal pass first, float32).  HBM-bound: algorithmic bytes = the nd * image_h * image_w output bytes.
-#include "kg_common.h"
+#include "label_common.h"        // kg_bits_ld, kg_check_bits_ld
 #include "lin_taps.h"
 #include <math.h>
 
@@ -78,11 +78,6 @@ extern "C" int kg_mask_paste(const float* flat, const int* dets, int nd, int inp
 // x >= W and the words from H * wpr on are zero.  A wave owns words: lane b evaluates pixel 64 k + b, __ballot forms the word, lane 0
 // stores it (a vector store).  Every block is 4 waves, every wave walks KG_BITS_WPW consecutive words of one mask.
 #define KG_BITS_WPW 8
-__host__ __device__ static inline long kg_bits_ld(int H, int W) {
-    const long nw = (long)H * ((W + 63) / 64);
-    return (nw + 1) & ~1L;
-}
-static inline bool kg_bits_ld_ok(int H, int W, long ld_words) { return ld_words >= kg_bits_ld(H, W) && ld_words % 2 == 0 && ld_words <= 0x7fffffffL; }
 static inline dim3 kg_bits_grid(int n, long ld_words) {
     return dim3((unsigned)((ld_words + 4 * KG_BITS_WPW - 1) / (4 * KG_BITS_WPW)), (unsigned)(n < 65535 ? n : 65535));
 }
@@ -144,8 +139,7 @@ extern "C" int kg_mask_paste_bits(const float* flat, const int* dets, int nd, in
                                   float seg_thresh, void* words, long ld_words, void* stream) {
     KG_CHECK_ARG(flat && dets && words, "kg_mask_paste_bits: null pointer");
     KG_CHECK_ARG(nd >= 0 && input_h > 0 && input_w > 0 && image_h > 0 && image_w > 0, "kg_mask_paste_bits: bad size");
-    KG_CHECK_ARG(kg_bits_ld_ok(image_h, image_w, ld_words), "kg_mask_paste_bits: ld_words %ld too small or odd (need %ld)", ld_words,
-                 kg_bits_ld(image_h, image_w));
+    KG_TRY(kg_check_bits_ld("kg_mask_paste_bits", image_h, image_w, ld_words));
     if (nd == 0) return KG_OK;
     hipLaunchKernelGGL(paste_bits_kernel, kg_bits_grid(nd, ld_words), dim3(256), 0, (hipStream_t)stream, flat, (const PasteDet*)dets, nd, input_h,
                        input_w, image_h, image_w, seg_thresh, (unsigned long long*)words, ld_words);
@@ -201,7 +195,7 @@ extern "C" long kg_mask_bits_ld(int H, int W) {
 extern "C" int kg_mask_pack_bits(const void* masks, int src_is_f32, int n, int H, int W, void* words, long ld_words, void* stream) {
     KG_CHECK_ARG(masks && words, "kg_mask_pack_bits: null pointer");
     KG_CHECK_ARG(n > 0 && H > 0 && W > 0, "kg_mask_pack_bits: bad size");
-    KG_CHECK_ARG(kg_bits_ld_ok(H, W, ld_words), "kg_mask_pack_bits: ld_words %ld too small or odd (need %ld)", ld_words, kg_bits_ld(H, W));
+    KG_TRY(kg_check_bits_ld("kg_mask_pack_bits", H, W, ld_words));
     if (src_is_f32)
         hipLaunchKernelGGL(pack_bits_kernel<float>, kg_bits_grid(n, ld_words), dim3(256), 0, (hipStream_t)stream, (const float*)masks, n, H, W,
                            (unsigned long long*)words, ld_words);
@@ -215,7 +209,7 @@ extern "C" int kg_mask_pack_bits(const void* masks, int src_is_f32, int n, int H
 extern "C" int kg_mask_unpack_bits(const void* words, long ld_words, int n, int H, int W, void* out, int out_is_u8, void* stream) {
     KG_CHECK_ARG(words && out, "kg_mask_unpack_bits: null pointer");
     KG_CHECK_ARG(n > 0 && H > 0 && W > 0, "kg_mask_unpack_bits: bad size");
-    KG_CHECK_ARG(kg_bits_ld_ok(H, W, ld_words), "kg_mask_unpack_bits: ld_words %ld too small or odd (need %ld)", ld_words, kg_bits_ld(H, W));
+    KG_TRY(kg_check_bits_ld("kg_mask_unpack_bits", H, W, ld_words));
     if (out_is_u8)
         hipLaunchKernelGGL(unpack_bits_kernel<unsigned char>, kg_bits_grid(n, ld_words), dim3(256), 0, (hipStream_t)stream,
                            (const unsigned long long*)words, ld_words, n, H, W, (unsigned char*)out);

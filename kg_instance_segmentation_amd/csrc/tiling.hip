@@ -5,14 +5,10 @@
 //                    that cover it
 //   kg_label_table   per-instance integers read back from the stitched map inside each instance's box
 //
-// The rules of instances.hip hold here too.  Every entry validates on the host before any HIP call and never synchronises.  Label and
-// pixel values read from device memory become stored values and predicates only, never part of an address.  The only addresses that
-// depend on a table are those of the grid origins (a HOST array, validated, passed by value in the kernel arguments) and of the job
-// boxes of kg_label_table (a device table the caller wrote; the kernel clamps every box to the map before it forms an address, so even
-// a wrong table cannot make it leave the buffer).  Plain C++ and vector memory operations only.
+// The index rule of label_common.h holds here.  The only addresses that depend on a table are those of the grid origins (a HOST array,
+// validated, passed by value in the kernel arguments) and of the job boxes of kg_label_table (kg_job_box).
 // Compiled with -ffp-contract=off: the tile input is float32(u8) / 255 - 0.5 as two float32 operations.
-#include "kg_common.h"
-#include <limits.h>
+#include "label_common.h"
 
 #define KG_TILE_MAX_AXIS 256        // tiles per axis: their origins travel by value in the kernel arguments (2 KB)
 struct TileGrid { int ys[KG_TILE_MAX_AXIS]; int xs[KG_TILE_MAX_AXIS]; };
@@ -97,52 +93,27 @@ __global__ __launch_bounds__(256) void tile_stitch_kernel(const int* __restrict_
 }
 
 // ---- table ----------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ long long tile_wave_sum(long long v) {
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ int tile_wave_min(int v) {
-    for (int o = 32; o; o >>= 1) { const int t = __shfl_xor(v, o); v = t < v ? t : v; }
-    return v;
-}
-__device__ __forceinline__ int tile_wave_max(int v) {
-    for (int o = 32; o; o >>= 1) { const int t = __shfl_xor(v, o); v = t > v ? t : v; }
-    return v;
-}
-
 // table[j] = {area_full[j] (0 without area_full), then over the pixels of the box of job j whose label equals its id: count, y1, x1, y2,
-// x2 (half-open; zeros if none), sum_y, sum_x}.  One block per job: its 256 threads walk the box as one flat row-major list (thread t
-// takes elements t, t + 256, ...; the position advances by additions, no division in the loop), so consecutive lanes read consecutive
-// pixels of a box row.  The box is clamped to the map first.  Integers only, reduced by shuffles and 256 bytes of LDS.
+// x2 (half-open; zeros if none), sum_y, sum_x}.  One block per job, walking its clamped box (kg_box_walk).  Integers only, reduced by
+// shuffles and 256 bytes of LDS.
 __global__ __launch_bounds__(256) void label_table_kernel(const int* __restrict__ labels, int H, int W, const int* __restrict__ jobs,
                                                           const long long* __restrict__ area_full, long long* __restrict__ table) {
     __shared__ long long part[4][8];
     const long j = blockIdx.x;
     const int* jb = jobs + j * 5;
     const int id = jb[0];
-    int by1 = jb[1], bx1 = jb[2], by2 = jb[3], bx2 = jb[4];
-    by1 = by1 < 0 ? 0 : by1; bx1 = bx1 < 0 ? 0 : bx1;
-    by2 = by2 > H ? H : by2; bx2 = bx2 > W ? W : bx2;
-    const int bh = by2 > by1 ? by2 - by1 : 0, bw = bx2 > bx1 ? bx2 - bx1 : 0;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     long long area = 0, sum_y = 0, sum_x = 0;
     int y1 = INT_MAX, x1 = INT_MAX, y2 = 0, x2 = 0;
-    if (bh > 0 && bw > 0) {
-        const int sy = 256 / bw, sx = 256 - sy * bw;
-        int yy = (int)threadIdx.x / bw, xx = (int)threadIdx.x - yy * bw;
-        while (yy < bh) {
-            const int Y = by1 + yy, X = bx1 + xx;
-            if (labels[(long)Y * W + X] == id) {
-                ++area; sum_y += Y; sum_x += X;
-                y1 = Y < y1 ? Y : y1; y2 = Y + 1 > y2 ? Y + 1 : y2;
-                x1 = X < x1 ? X : x1; x2 = X + 1 > x2 ? X + 1 : x2;
-            }
-            xx += sx; yy += sy;
-            if (xx >= bw) { xx -= bw; ++yy; }
+    kg_box_walk(kg_job_box(jb + 1, H, W), [&](int Y, int X) {
+        if (labels[(long)Y * W + X] == id) {
+            ++area; sum_y += Y; sum_x += X;
+            y1 = Y < y1 ? Y : y1; y2 = Y + 1 > y2 ? Y + 1 : y2;
+            x1 = X < x1 ? X : x1; x2 = X + 1 > x2 ? X + 1 : x2;
         }
-    }
-    area = tile_wave_sum(area); sum_y = tile_wave_sum(sum_y); sum_x = tile_wave_sum(sum_x);
-    y1 = tile_wave_min(y1); x1 = tile_wave_min(x1); y2 = tile_wave_max(y2); x2 = tile_wave_max(x2);
+    });
+    area = kg_wave_sum(area); sum_y = kg_wave_sum(sum_y); sum_x = kg_wave_sum(sum_x);
+    y1 = kg_wave_min(y1); x1 = kg_wave_min(x1); y2 = kg_wave_max(y2); x2 = kg_wave_max(x2);
     if (lane == 0) {
         long long* p = part[wave];
         p[0] = 0; p[1] = area; p[2] = y1; p[3] = x1; p[4] = y2; p[5] = x2; p[6] = sum_y; p[7] = sum_x;
@@ -150,17 +121,8 @@ __global__ __launch_bounds__(256) void label_table_kernel(const int* __restrict_
     __syncthreads();
     if (threadIdx.x < 8) {
         const int c = threadIdx.x;
-        long long v = part[0][c];
-        for (int w = 1; w < 4; ++w) {
-            const long long t = part[w][c];
-            if (c == 2 || c == 3) v = t < v ? t : v;
-            else if (c == 4 || c == 5) v = t > v ? t : v;
-            else v += t;
-        }
-        const long long visible = part[0][1] + part[1][1] + part[2][1] + part[3][1];
-        if (visible == 0 && c >= 2 && c <= 5) v = 0;
-        if (c == 0) v = area_full ? area_full[j] : 0;
-        table[j * 8 + c] = v;
+        const long long v = kg_block_combine<8>(part, c, kg_table_col_kind(c), 1);
+        table[j * 8 + c] = c == 0 ? (area_full ? area_full[j] : 0) : v;
     }
 }
 
@@ -176,11 +138,9 @@ static int tile_axis_check(const char* fn, const char* axis, const int* o, int n
 // the grid of kg_tile_cut / kg_tile_stitch: nothing is launched unless all of it holds
 static int tile_grid_check(const char* fn, const int* ys, int ny, const int* xs, int nx, int th, int tw, int H, int W, TileGrid* g) {
     KG_CHECK_ARG(H > 0 && W > 0 && th > 0 && tw > 0, "%s: bad size (H %d, W %d, th %d, tw %d)", fn, H, W, th, tw);
-    KG_CHECK_ARG((long)H * W <= 0x7fffffffL, "%s: H * W exceeds 2^31 - 1", fn);
-    int rc = tile_axis_check(fn, "y", ys, ny, H);
-    if (rc != KG_OK) return rc;
-    rc = tile_axis_check(fn, "x", xs, nx, W);
-    if (rc != KG_OK) return rc;
+    KG_TRY(kg_check_map_size(fn, H, W));
+    KG_TRY(tile_axis_check(fn, "y", ys, ny, H));
+    KG_TRY(tile_axis_check(fn, "x", xs, nx, W));
     KG_CHECK_ARG((long)ny * nx * th <= 0x7fffffffL / tw, "%s: ny * nx * th * tw exceeds 2^31 - 1", fn);
     memset(g, 0, sizeof(*g));
     for (int i = 0; i < ny; ++i) g->ys[i] = ys[i];
@@ -192,10 +152,9 @@ static int tile_grid_check(const char* fn, const int* ys, int ny, const int* xs,
 extern "C" int kg_tile_cut(const void* image, int H, int W, const int* ys, int ny, const int* xs, int nx, int th, int tw, float* out, void* stream) {
     KG_CHECK_ARG(image && out, "kg_tile_cut: null pointer");
     TileGrid g;
-    const int rc = tile_grid_check("kg_tile_cut", ys, ny, xs, nx, th, tw, H, W, &g);
-    if (rc != KG_OK) return rc;
+    KG_TRY(tile_grid_check("kg_tile_cut", ys, ny, xs, nx, th, tw, H, W, &g));
     KG_CHECK_ARG(tw % 4 == 0, "kg_tile_cut: tw %d is not a multiple of 4", tw);
-    KG_CHECK_ARG(((unsigned long long)(size_t)out & 15) == 0, "kg_tile_cut: out must be 16-byte aligned");
+    KG_CHECK_ARG(kg_aligned(out, 15), "kg_tile_cut: out must be 16-byte aligned");
     hipLaunchKernelGGL(tile_cut_kernel, dim3((unsigned)kg_cdiv((long)th * (tw >> 2), 256), (unsigned)nx, (unsigned)ny), dim3(256), 0, (hipStream_t)stream,
                        (const unsigned char*)image, H, W, g, th, tw, out);
     KG_CHECK_LAUNCH("tile_cut");
@@ -206,10 +165,10 @@ extern "C" int kg_tile_cut(const void* image, int H, int W, const int* ys, int n
 extern "C" int kg_bitmask_clip(void* words, long ld_words, int n, int H, int W, int vh, int vw, void* stream) {
     KG_CHECK_ARG(H > 0 && W > 0 && n >= 0, "kg_bitmask_clip: bad size (H %d, W %d, n %d)", H, W, n);
     KG_CHECK_ARG(vh >= 0 && vh <= H && vw >= 0 && vw <= W, "kg_bitmask_clip: window %d x %d outside the %d x %d masks", vh, vw, H, W);
-    const long wpr = (W + 63) / 64, nw = (long)H * wpr, need = (nw + 1) & ~1L;
-    KG_CHECK_ARG(ld_words % 2 == 0 && ld_words >= need && ld_words <= 0x7fffffffL, "kg_bitmask_clip: ld_words %ld too small or odd (need %ld)", ld_words, need);
+    const long nw = (long)H * ((W + 63) / 64);
+    KG_TRY(kg_check_bits_ld("kg_bitmask_clip", H, W, ld_words));
     KG_CHECK_ARG(words || n == 0, "kg_bitmask_clip: null pointer (words)");
-    KG_CHECK_ARG(((unsigned long long)(size_t)words & 15) == 0, "kg_bitmask_clip: words must be 16-byte aligned");
+    KG_CHECK_ARG(kg_aligned(words, 15), "kg_bitmask_clip: words must be 16-byte aligned");
     KG_CHECK_ARG((long)n <= LONG_MAX / 8 / ld_words, "kg_bitmask_clip: n * ld_words too large");
     if (n == 0 || (vh == H && vw == W)) return KG_OK;
     hipLaunchKernelGGL(bitmask_clip_kernel, dim3((unsigned)kg_cdiv(nw, 256), (unsigned)(n < 65535 ? n : 65535)), dim3(256), 0, (hipStream_t)stream,
@@ -223,8 +182,7 @@ extern "C" int kg_tile_stitch(const int* tile_labels, const int* ys, int ny, con
                               void* stream) {
     KG_CHECK_ARG(tile_labels && labels, "kg_tile_stitch: null pointer");
     TileGrid g;
-    const int rc = tile_grid_check("kg_tile_stitch", ys, ny, xs, nx, th, tw, H, W, &g);
-    if (rc != KG_OK) return rc;
+    KG_TRY(tile_grid_check("kg_tile_stitch", ys, ny, xs, nx, th, tw, H, W, &g));
     KG_CHECK_ARG(kg_cdiv(W, 256) <= 65535, "kg_tile_stitch: W %d too large", W);
     hipLaunchKernelGGL(tile_stitch_kernel, dim3((unsigned)H, (unsigned)kg_cdiv(W, 256)), dim3(256), 0, (hipStream_t)stream, tile_labels, g, ny, nx, th,
                        tw, H, W, labels);
@@ -236,11 +194,10 @@ extern "C" int kg_tile_stitch(const int* tile_labels, const int* ys, int ny, con
 // int64 [n] or NULL; table: device int64 [n][8]
 extern "C" int kg_label_table(const int* labels, int H, int W, const int* jobs, int n, const long long* area_full, long long* table, void* stream) {
     KG_CHECK_ARG(H > 0 && W > 0 && n >= 0, "kg_label_table: bad size (H %d, W %d, n %d)", H, W, n);
-    KG_CHECK_ARG((long)H * W <= 0x7fffffffL, "kg_label_table: H * W exceeds 2^31 - 1");
+    KG_TRY(kg_check_map_size("kg_label_table", H, W));
     KG_CHECK_ARG(labels, "kg_label_table: null pointer (labels)");
     KG_CHECK_ARG((jobs && table) || n == 0, "kg_label_table: null pointer (jobs / table)");
-    KG_CHECK_ARG((((unsigned long long)(size_t)labels | (unsigned long long)(size_t)jobs) & 3) == 0 &&
-                 (((unsigned long long)(size_t)area_full | (unsigned long long)(size_t)table) & 7) == 0, "kg_label_table: misaligned pointer");
+    KG_CHECK_ARG(kg_aligned(labels, 3) && kg_aligned(jobs, 3) && kg_aligned(area_full, 7) && kg_aligned(table, 7), "kg_label_table: misaligned pointer");
     if (n == 0) return KG_OK;
     hipLaunchKernelGGL(label_table_kernel, dim3((unsigned)n), dim3(256), 0, (hipStream_t)stream, labels, H, W, jobs, area_full, table);
     KG_CHECK_LAUNCH("label_table");

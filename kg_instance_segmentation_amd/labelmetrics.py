@@ -24,6 +24,7 @@ Semantics
 import numpy as np
 
 from . import _lib, evaluation, instances
+from ._labelmaps import device_jobs, device_maps, host_maps, is_device
 from .bitmasks import BitMasks, unpack_host
 
 KGLibraryError = _lib.KGLibraryError
@@ -57,13 +58,6 @@ class Contingency:
 
 # ---- host statements of the semantics ---------------------------------------------------------------------------------------------------
 
-def _host_map(fn, labels):
-    lab = np.asarray(labels)
-    if lab.ndim != 2 or lab.dtype.kind not in "iu" or lab.size == 0:
-        raise KGLibraryError(f"{fn}: a label map must be a non-empty integer array [H, W]")
-    return lab
-
-
 def _count(fn, n):
     if int(n) != n or not 0 <= int(n) < 2 ** 31 // 5:
         raise KGLibraryError(f"{fn}: instance count {n}")
@@ -72,7 +66,7 @@ def _count(fn, n):
 
 def label_stats_counts_host(labels, n):
     """(stats int64 [n, 5], invalid): the raw entry's two outputs -- the stats of every valid id are exact whatever the other pixels hold."""
-    lab = _host_map("label_stats_host", labels).astype(np.int64)
+    lab = host_maps("label_stats_host", labels, False).astype(np.int64)
     n = _count("label_stats_host", n)
     ys, xs = np.nonzero((lab >= 1) & (lab <= n))
     ids = lab[ys, xs] - 1
@@ -154,7 +148,7 @@ def split_jobs(jobs, max_job_pixels=65536):
 
 def inter_jobs_host(a, b, jobs):
     """int64 [m]: per job (id_a, id_b, y1, x1, y2, x2) the pixels of the box, clamped to the map, with a == id_a and b == id_b."""
-    a, b = _host_map("inter_jobs_host", a), _host_map("inter_jobs_host", b)
+    a, b = host_maps("inter_jobs_host", a, False), host_maps("inter_jobs_host", b, False)
     if a.shape != b.shape:
         raise KGLibraryError(f"inter_jobs_host: maps of {a.shape} and {b.shape}")
     H, W = a.shape
@@ -168,7 +162,7 @@ def inter_jobs_host(a, b, jobs):
 
 def contingency_host(pred, gt, n_pred, n_gt):
     """The Contingency of two host label maps: ONE np.unique over pred * (n_gt + 1) + gt."""
-    p, g = _host_map("contingency_host", pred), _host_map("contingency_host", gt)
+    p, g = host_maps("contingency_host", pred, False), host_maps("contingency_host", gt, False)
     n_pred, n_gt = _count("contingency_host", n_pred), _count("contingency_host", n_gt)
     if p.shape != g.shape:
         raise KGLibraryError(f"contingency_host: a predicted map of {p.shape} against a ground truth of {g.shape}")
@@ -185,20 +179,11 @@ def contingency_host(pred, gt, n_pred, n_gt):
 
 # ---- device -----------------------------------------------------------------------------------------------------------------------------
 
-def _device_map(fn, t):
-    import torch
-    if not torch.is_tensor(t) or t.device.type != "cuda":
-        raise KGLibraryError(f"{fn} (MI355X build) needs the label map on a GPU device; the host route is {fn}_host")
-    if t.dtype != torch.int32 or t.dim() != 2 or t.numel() == 0:
-        raise KGLibraryError(f"{fn}: a label map must be a non-empty int32 tensor [H, W]")
-    return t.contiguous()
-
-
 def _stats_buffer(labels, n):
     """device int32 [5 n + 1]: the stats of kg_label_stats with its invalid count behind them (one buffer, so one copy brings both back)"""
     import torch
     from ._lib import ptr, stream_ptr
-    lab = _device_map("label_stats", labels)
+    lab = device_maps("label_stats", labels, False)
     n = _count("label_stats", n)
     buf = torch.empty(n * 5 + 1, dtype=torch.int32, device=lab.device)
     with torch.cuda.device(lab.device):
@@ -223,21 +208,12 @@ def label_stats(labels, n):
 def inter_jobs(a, b, jobs):
     """a, b: device int32 [H, W]; jobs: host int [m, 6] (uploaded once) or a device int32 tensor -> device int64 [m] (kg_label_inter_jobs)."""
     import torch
-    from . import ops
     from ._lib import ptr, stream_ptr
-    a, b = _device_map("inter_jobs", a), _device_map("inter_jobs", b)
+    a, b = device_maps("inter_jobs", a, False), device_maps("inter_jobs", b, False)
     if a.shape != b.shape or a.device != b.device:
         raise KGLibraryError(f"inter_jobs: maps of {tuple(a.shape)} and {tuple(b.shape)} must have one size and one device")
     dev = a.device
-    if torch.is_tensor(jobs):
-        if jobs.dtype != torch.int32 or jobs.dim() != 2 or jobs.shape[1] != 6 or jobs.device != dev:
-            raise KGLibraryError("inter_jobs: device jobs must be int32 [m, 6] on the maps' device")
-        jd = jobs.contiguous()
-    else:
-        j = np.asarray(jobs)
-        if j.ndim != 2 or j.shape[1] != 6 or j.dtype.kind not in "iu" or (j.size and (j.min() < -2 ** 31 or j.max() > 2 ** 31 - 1)):
-            raise KGLibraryError("inter_jobs: jobs must be integers [m, 6] = (id_a, id_b, y1, x1, y2, x2) that fit int32")
-        jd = ops.h2d(np.ascontiguousarray(j.astype(np.int32)), dev) if len(j) else torch.empty(0, 6, dtype=torch.int32, device=dev)
+    jd = device_jobs("inter_jobs", jobs, 6, "(id_a, id_b, y1, x1, y2, x2)", dev)
     m = jd.shape[0]
     count = torch.empty(m, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
@@ -250,7 +226,7 @@ def contingency(pred, gt, n_pred, n_gt, pred_stats=None, gt_stats=None, max_job_
     (STATS_COLUMNS) when the caller has them -- columns 1:6 of an Instances / TiledInstances table are the stats of its label map -- and
     then no stats launch is made for that side.  A box of more than max_job_pixels pixels is counted in bands (split_jobs).
     Device -> host copies: one for the counts, and one for each side whose stats were computed here."""
-    pred, gt = _device_map("contingency", pred), _device_map("contingency", gt)
+    pred, gt = device_maps("contingency", pred, False), device_maps("contingency", gt, False)
     n_pred, n_gt = _count("contingency", n_pred), _count("contingency", n_gt)
     if pred.shape != gt.shape or pred.device != gt.device:
         raise KGLibraryError(f"contingency: a predicted map of {tuple(pred.shape)} against a ground truth of {tuple(gt.shape)} (one size, one device)")
@@ -370,7 +346,7 @@ class LabelEvaluator:
         else:
             raise KGLibraryError("LabelEvaluator.add: pred must be an Instances or a (labels, n_pred) pair")
         import torch
-        on_device = torch.is_tensor(plab) and plab.device.type == "cuda"
+        on_device = is_device(plab)
         if torch.is_tensor(plab) and not on_device:
             plab = plab.numpy()
         shape = tuple(plab.shape)
@@ -394,7 +370,7 @@ class LabelEvaluator:
         if _is_map_pair(gt):
             lab, n = gt[0], int(gt[1])
             if not torch.is_tensor(lab):
-                lab = ops.h2d(np.ascontiguousarray(_host_map("LabelEvaluator.add", lab).astype(np.int32)), dev)
+                lab = ops.h2d(np.ascontiguousarray(host_maps("LabelEvaluator.add", lab, False).astype(np.int32)), dev)
             return lab.to(dev), n, None
         m = BitMasks.from_dense(gt, dev)                             # (a BitMasks passes through)
         if m.device != dev:
@@ -407,7 +383,7 @@ class LabelEvaluator:
         import torch
         if _is_map_pair(gt):
             lab = gt[0].cpu().numpy() if torch.is_tensor(gt[0]) else gt[0]
-            return _host_map("LabelEvaluator.add", lab), int(gt[1])
+            return host_maps("LabelEvaluator.add", lab, False), int(gt[1])
         if isinstance(gt, BitMasks):
             dense = unpack_host(gt.words_cpu(), gt.h, gt.w)
         else:

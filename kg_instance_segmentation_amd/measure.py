@@ -33,7 +33,8 @@ import math
 
 import numpy as np
 
-from . import _lib, labelmetrics
+from . import _lib, _labelmaps, labelmetrics
+from ._labelmaps import is_device
 from .labelmetrics import split_jobs  # noqa: F401  (the band rule is labelmetrics': columns 0 and 1 of a job pass through it untouched)
 
 KGLibraryError = _lib.KGLibraryError
@@ -138,20 +139,12 @@ class Measurements:
 
 # ---- host statement of the semantics ----------------------------------------------------------------------------------------------------
 
-def _host_maps(fn, labels):
-    lab = np.asarray(labels)
-    if lab.ndim not in (2, 3) or lab.dtype.kind not in "iu" or lab.size == 0:
-        raise KGLibraryError(f"{fn}: label maps must be a non-empty integer array [H, W] or [nimg, H, W]")
-    maps = lab.reshape((-1,) + lab.shape[-2:])
-    _sizes(fn, *maps.shape)
-    return maps, lab.ndim == 2
-
-
-def _sizes(fn, nimg, H, W):
+def _side(fn, maps):
+    """[nimg, H, W] maps (host or device) as they came, once their sides are known to fit"""
+    H, W = maps.shape[-2:]
     if H > MAX_SIDE or W > MAX_SIDE:
         raise KGLibraryError(f"{fn}: a map of {H} x {W} exceeds {MAX_SIDE} (the bound that keeps every sum inside int64)")
-    if nimg * H * W > 2 ** 31 - 1:
-        raise KGLibraryError(f"{fn}: nimg * H * W exceeds 2^31 - 1")
+    return maps
 
 
 def _host_image(fn, image, shape):
@@ -168,11 +161,11 @@ def _host_image(fn, image, shape):
     return a
 
 
+_JOB_COLUMNS = "(img, id, y1, x1, y2, x2)"
+
+
 def _host_jobs(fn, jobs):
-    j = np.asarray(jobs)
-    if j.ndim != 2 or j.shape[1] != 6 or j.dtype.kind not in "iu" or (j.size and (j.min() < -2 ** 31 or j.max() > 2 ** 31 - 1)):
-        raise KGLibraryError(f"{fn}: jobs must be integers [m, 6] = (img, id, y1, x1, y2, x2) that fit int32")
-    return j.astype(np.int64)
+    return _labelmaps.host_jobs(fn, jobs, 6, _JOB_COLUMNS).astype(np.int64)
 
 
 def jobs_from_stats(stats, img=0):
@@ -198,7 +191,7 @@ def measure_host(labels, jobs_or_n, image=None):
     """labels: integers [H, W] or [nimg, H, W]; jobs_or_n: jobs [m, 6] = (img, id, y1, x1, y2, x2), or the instance count n (one per map
     for a stack): the ids 1 .. n are then measured inside their own boxes (labelmetrics.label_stats_host, which raises when a pixel lies
     outside [0, n]); image: None, or uint8 / uint16 [H, W, C] / [nimg, H, W, C] -> int64 [m, 10 + 4 C], one row per job, nothing split."""
-    maps, _ = _host_maps("measure_host", labels)
+    maps = _side("measure_host", _labelmaps.host_maps("measure_host", labels, True)[0])
     nimg, H, W = maps.shape
     img = _host_image("measure_host", image, maps.shape)
     C = 0 if img is None else img.shape[3]
@@ -260,14 +253,8 @@ def combine_bands(rows, owner, n_jobs):
 # ---- device -----------------------------------------------------------------------------------------------------------------------------
 
 def _device_maps(fn, t):
-    import torch
-    if not torch.is_tensor(t) or t.device.type != "cuda":
-        raise KGLibraryError(f"{fn} (MI355X build) needs the label maps on a GPU device; the host route is {fn}_host")
-    if t.dtype != torch.int32 or t.dim() not in (2, 3) or t.numel() == 0:
-        raise KGLibraryError(f"{fn}: label maps must be a non-empty int32 tensor [H, W] or [nimg, H, W]")
-    H, W = t.shape[-2:]
-    _sizes(fn, t.numel() // (H * W), H, W)
-    return t.contiguous().view(-1, H, W)
+    t = _labelmaps.device_maps(fn, t, True)
+    return _side(fn, t.view((-1,) + t.shape[-2:]))
 
 
 def _device_image(fn, image, shape, dev):
@@ -296,20 +283,13 @@ def measure_rows(labels, jobs, image=None):
     tensor; image None, a host array (uploaded once) or a device tensor -> device int64 [m, 10 + 4 C].  One launch, no copy back, no
     synchronisation, nothing split."""
     import torch
-    from . import ops
     from ._lib import ptr, stream_ptr
     lab = _device_maps("measure", labels)
     dev = lab.device
     nimg, H, W = lab.shape
     img = _device_image("measure", image, lab.shape, dev)
     C = 0 if img is None else img.shape[3]
-    if torch.is_tensor(jobs):
-        if jobs.dtype != torch.int32 or jobs.dim() != 2 or jobs.shape[1] != 6 or jobs.device != dev:
-            raise KGLibraryError("measure: device jobs must be int32 [m, 6] on the maps' device")
-        jd = jobs.contiguous()
-    else:
-        j = _host_jobs("measure", jobs)
-        jd = ops.h2d(np.ascontiguousarray(j.astype(np.int32)), dev) if len(j) else torch.empty(0, 6, dtype=torch.int32, device=dev)
+    jd = _labelmaps.device_jobs("measure", jobs, 6, _JOB_COLUMNS, dev)
     m = jd.shape[0]
     out = torch.empty(m, 10 + 4 * C, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
@@ -352,11 +332,6 @@ def measure(labels, n=None, jobs=None, image=None, stats=None, max_job_pixels=65
     return Measurements(combine_bands(rows, owner, len(j)))
 
 
-def _is_device(t):
-    import torch
-    return torch.is_tensor(t) and t.device.type == "cuda"
-
-
 def measure_instances(inst, image=None, max_job_pixels=65536):
     """measure for an Instances / TiledInstances -> Measurements with len(inst) rows: ids 1 .. n, boxes from table[:, 2:6]; an instance
     with area_visible == 0 gets a row of zeros.  image: None, or uint8 / uint16 [H, W, C] at the label map's size (host array or device
@@ -368,7 +343,7 @@ def measure_instances(inst, image=None, max_job_pixels=65536):
     stats = np.asarray(inst.table, np.int64).reshape(-1, 8)[:, 1:6]
     if len(stats) != len(inst):
         raise KGLibraryError(f"measure_instances: a table of {len(stats)} rows for {len(inst)} instances")
-    if _is_device(inst.labels):
+    if is_device(inst.labels):
         return measure(inst.labels, len(inst), image=image, stats=stats, max_job_pixels=max_job_pixels)
     lab = inst.labels.numpy() if torch.is_tensor(inst.labels) else inst.labels
     if torch.is_tensor(image):

@@ -32,6 +32,7 @@ An object larger than the overlap is cut at the edge of the tile that owns its c
 import numpy as np
 
 from . import _lib, instances
+from ._labelmaps import device_jobs, is_device, upload_jobs
 from .bitmasks import BitMasks
 from .instances import Instances
 
@@ -330,8 +331,7 @@ def assemble_host(plan, per_tile_preds, nms_thresh=0.5):
 # ---- device -------------------------------------------------------------------------------------------------------------------------------
 
 def _cuda(fn, t, dtype, what):
-    import torch
-    if not torch.is_tensor(t) or t.device.type != "cuda":
+    if not is_device(t):
         raise KGLibraryError(f"{fn} (MI355X build) needs {what} on a GPU device; the host route is {fn}_host")
     if t.dtype != dtype:
         raise KGLibraryError(f"{fn}: {what} must be {dtype}")
@@ -389,7 +389,6 @@ def table_from_labels(labels, jobs, area_full=None):
     """labels: device int32 [H, W]; jobs: host int [n, 5] = (id, y1, x1, y2, x2), validated here and uploaded once (or a device int32
     tensor the caller built from validated boxes); area_full: device int64 [n] or None -> device int64 [n, 8] (kg_label_table)."""
     import torch
-    from . import ops
     from ._lib import ptr, stream_ptr
     lab = _cuda("table_from_labels", labels, torch.int32, "the label map")
     if lab.dim() != 2:
@@ -397,12 +396,9 @@ def table_from_labels(labels, jobs, area_full=None):
     H, W = lab.shape
     dev = lab.device
     if torch.is_tensor(jobs):
-        jd = _cuda("table_from_labels", jobs, torch.int32, "device jobs")
-        if jd.dim() != 2 or jd.shape[1] != 5 or jd.device != dev:
-            raise KGLibraryError("table_from_labels: device jobs must be int32 [n, 5] on the labels' device")
+        jd = device_jobs("table_from_labels", _cuda("table_from_labels", jobs, torch.int32, "device jobs"), 5, "", dev, "n", "labels'")
     else:
-        j = _jobs(jobs, H, W)
-        jd = ops.h2d(j, dev) if len(j) else torch.empty(0, 5, dtype=torch.int32, device=dev)
+        jd = upload_jobs(_jobs(jobs, H, W), dev)                     # _jobs is the stricter validation: nothing is scanned twice
     n = jd.shape[0]
     if area_full is not None:
         area_full = _cuda("table_from_labels", area_full, torch.int64, "area_full")

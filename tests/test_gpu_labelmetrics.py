@@ -116,6 +116,33 @@ def test_inter_jobs():
     assert np.array_equal(lm.inter_jobs(up(wide_a), up(wide_b), np.array(jobs)).cpu().numpy(), want) and want[0] >= 700
 
 
+def test_inter_jobs_box_widths_around_the_walk():
+    H, W = 40, 300
+    a, b = np.full((H, W), 1, np.int32), np.full((H, W), 2, np.int32)
+    jobs = np.array([[1, 2, 3, 7, 40, 7 + w] for w in (1, 2, 255, 256, 257)] + [[1, 2, H - 1, 0, H, W], [1, 2, 0, W - 1, H, W]], np.int32)
+    want = lm.inter_jobs_host(a, b, jobs)
+    assert want.tolist() == [37, 74, 37 * 255, 37 * 256, 37 * 257, W, H]
+    assert np.array_equal(lm.inter_jobs(up(a), up(b), jobs).cpu().numpy(), want)
+
+
+def test_inter_jobs_grid_stride():
+    """More jobs than the grid cap of 2^20 blocks: the blocks stride, and every copy of one small job gives the single job's count."""
+    from kg_instance_segmentation_amd import _lib
+    from kg_instance_segmentation_amd._lib import ptr, stream_ptr
+    H, W, m = 9, 70, 2 ** 20 + 3
+    a, b = np.zeros((H, W), np.int32), np.zeros((H, W), np.int32)
+    a[3:5, 10:13], b[3:5, 11:14] = 4, 3
+    job = np.array([[4, 3, 3, 10, 5, 14]], np.int32)                                          # 8 pixels, 4 of them counted
+    want = lm.inter_jobs_host(a, b, job)
+    assert want.tolist() == [4]
+    ad, bd = up(a), up(b)
+    assert np.array_equal(lm.inter_jobs(ad, bd, job).cpu().numpy(), want)
+    guard = torch.full((m + 2,), -7, dtype=torch.int64, device=DEV)                           # a cell in front of and behind the output
+    jd = up(job).repeat(m, 1)
+    _lib.call("kg_label_inter_jobs", ptr(ad), ptr(bd), H, W, ptr(jd), m, ptr(guard[1:]), stream_ptr())
+    assert bool((guard[1:-1] == int(want[0])).all()) and int(guard[0]) == -7 and int(guard[-1]) == -7
+
+
 # ---- contingency ------------------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("H,W", SHAPES)

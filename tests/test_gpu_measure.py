@@ -115,6 +115,25 @@ def test_hostile_job_table():
     assert ms.measure_rows(d, np.zeros((0, 6), np.int64), img).shape == (0, 18)          # m == 0 launches nothing
 
 
+def test_grid_stride():
+    """More jobs than the grid cap of 2^20 blocks (C = 0): the blocks stride, and every copy of one small job gives the single job's row."""
+    H, W, m = 9, 70, 2 ** 20 + 3
+    lab = np.zeros((H, W), np.int32)
+    lab[3:5, 10:13] = 4
+    lab[4, 13] = 2
+    job = np.array([[0, 4, 3, 10, 5, 14]], np.int32)                 # 8 pixels, 6 of them the id's
+    want = ms.measure_host(lab, job)
+    assert want[0, :3].tolist() == [6, 21, 66] and want[0, 8] > 0
+    d = up(lab)
+    one = ms.measure_rows(d, job)
+    assert np.array_equal(one.cpu().numpy(), want)
+    guard = torch.full((m + 2, 10), -7, dtype=torch.int64, device=DEV)                      # rows in front of and behind the output
+    from kg_instance_segmentation_amd._lib import ptr, stream_ptr
+    jd = up(job).repeat(m, 1)
+    _lib.call("kg_label_measure", ptr(d), 1, H, W, None, 0, 1, ptr(jd), m, ptr(guard[1:]), stream_ptr())
+    assert bool((guard[1:-1] == one).all()) and bool((guard[0] == -7).all()) and bool((guard[-1] == -7).all())
+
+
 def test_extreme_label_values_are_contact():
     lab = np.zeros((9, 70), np.int32)
     lab[3:6, 10:60] = 5

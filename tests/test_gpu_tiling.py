@@ -158,6 +158,17 @@ def test_table(n):
             tiling.table_from_labels(lab_d, np.array([[1, 0, 0, H + 1, W]]))
 
 
+def test_table_box_widths_around_the_walk():
+    H, W = 40, 300
+    lab = np.ones((H, W), np.int32)
+    jobs = np.array([[1, 3, 7, 40, 7 + w] for w in (1, 2, 255, 256, 257)] + [[1, H - 1, 0, H, W], [1, 0, W - 1, H, W]], np.int32)
+    want = tiling.table_from_labels_host(lab, jobs)
+    assert want[:, 1].tolist() == [37, 74, 37 * 255, 37 * 256, 37 * 257, W, H]
+    assert want[4].tolist() == [0, 37 * 257, 3, 7, 40, 264, 257 * sum(range(3, 40)), 37 * sum(range(7, 264))]
+    got = tiling.table_from_labels(torch.from_numpy(lab).to(DEV), jobs).cpu().numpy()
+    assert np.array_equal(got, want)
+
+
 def test_table_sums_of_a_full_image():
     """One instance over a whole 1040 x 1388 map, one job over all of it: sum_y is 749 478 240 and sum_x 1 001 081 120 from 1 443 520
     pixels in ONE workgroup; a second job over a 1040 x 2100 map passes 2^31."""
