@@ -469,6 +469,36 @@ int kg_component_remap(const int* comp, int nimg, int H, int W, const int* comp_
  * synchronises. */
 int kg_label_measure(const int* labels, int nimg, int H, int W, const void* image, int channels, int elem_bytes, const int* jobs, int m,
                      long long* out, void* stream);
+/* Nearest-other-label distance maps (csrc/distance.hip; distance.py states the semantics in NumPy): expand, ring, shrink, inscribed circle.
+ * THE TRANSFORM.  labels = device int32 [nimg][H][W], ANY int32 values (compared only); max_d2 in 1 .. 4096, R = floor(sqrt(max_d2)) <= 64.
+ * For a pixel p with value v, C(p) = the pixels q of the SAME image with labels[q] != v and |p - q|^2 <= max_d2; d2[p] = the smallest
+ * |p - q|^2 over C(p) and nearest[p] = the smallest value (signed compare) among the q of C(p) at that distance; with C(p) empty
+ * d2[p] = max_d2 + 1 ("saturated") and nearest[p] = v.  With frame != 0 the four sides of the image count as another value for d2 only:
+ * f = min(y + 1, x + 1, H - y, W - x), and where f^2 <= max_d2, d2[p] = min(d2[p], f^2).  No order of execution changes the result.
+ * kg_label_distance: d2, nearest = device int32 [nimg][H][W], every element written; either may be NULL (that output is skipped), not
+ * both; neither may alias labels or the other.
+ * kg_label_regrow: the same computation, only a result map reaches memory.  Needs 0 <= lo2 <= hi2 <= max_d2.
+ *   op 0 (expand)  out = nearest where labels == 0 && d2 <= hi2, else labels; lo2 == 0, frame == 0
+ *   op 1 (ring)    out = nearest where labels == 0 && lo2 < d2 <= hi2, else 0; frame == 0
+ *   op 2 (shrink)  out = labels where labels != 0 && d2 > hi2, else 0; lo2 == 0, frame honoured
+ * out may not alias labels.
+ * kg_label_inscribed: d2 = kg_label_distance's map; jobs = device int32 [m][6] rows {img, id, y1, x1, y2, x2} (half-open box), the layout of
+ * kg_label_measure -> out = device int32 [m][4] rows {d2max, y, x, count} over the pixels of the clamped box with labels == id: the
+ * largest d2, the pixel with the smallest y * W + x among those that attain it, the pixel count; {0, -1, -1, 0} for a job with no pixel.
+ * These rows are NOT additive over bands: the host takes the largest d2max, then the smallest index, and adds the counts.
+ * SIZE RULE.  max_d2 <= 4096: a candidate distance is at most 8192, d2 <= 4097, a vertical run distance <= 64 fits a byte; nimg * H * W
+ * <= 2^31 - 1: every pixel index fits int32.
+ * INDEX RULE.  Labels and d2 values are predicates and stored values only; a row or column outside the image is decided by a predicate on
+ * its coordinates before any address is formed; every loop is bounded by a kernel argument or a constant.  The job table is the one
+ * device-read table: its box is clamped to the map before any address is formed and its image index is used only inside
+ * (unsigned)img < (unsigned)nimg.  No atomics.
+ * One launch per 65535 images (the image index is a grid dimension) for distance and regrow; one launch whatever m is for inscribed, and
+ * m == 0 is valid and launches nothing (jobs and out may then be NULL).  All three validate on the host before any HIP call (null
+ * pointers, nimg, H, W > 0, nimg * H * W <= 2^31 - 1, max_d2, op, lo2 / hi2, frame against op, 4-byte alignment, aliasing, m >= 0) and
+ * never synchronise. */
+int kg_label_distance(const int* labels, int nimg, int H, int W, int max_d2, int frame, int* d2, int* nearest, void* stream);
+int kg_label_regrow(const int* labels, int nimg, int H, int W, int max_d2, int frame, int op, int lo2, int hi2, int* out, void* stream);
+int kg_label_inscribed(const int* labels, const int* d2, int nimg, int H, int W, const int* jobs, int m, int* out, void* stream);
 
 /* ---- per-box segmentation branch (KGnet.py:246-267, 321-350): ragged row bookkeeping ---- */
 int kg_seg_build_rows(const int* boxtab8, int nb, int* rowdesc, int* row2box, int* srcrow, void* stream);

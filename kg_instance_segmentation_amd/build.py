@@ -46,6 +46,7 @@ SOURCES = {
     "labelmetrics.hip": [],
     "components.hip": [],
     "measure.hip": [],
+    "distance.hip": [],
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function"]

@@ -118,11 +118,14 @@ def instances_from_predictions(preds):
     return out
 
 
-def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None, max_workspace_bytes=None, clean=None, measure=None):
+def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None, max_workspace_bytes=None, clean=None, measure=None,
+                      expand=None):
     """predict(packed=True) followed by the instance label map and the per-instance table of every image (instances.py), on the device:
     the label map (4 bytes per pixel) and the table (64 bytes per instance) replace n full-size masks as what crosses to the host.
     clean: None, or a dict of components.clean's policy arguments: every label map is then cleaned on the device (one components pass
     over all images of one output size) and the tables are refreshed.
+    expand: None, or a distance in pixels (a number, at most 64): every instance is then grown by that much without two instances
+    merging (distance.expand_instances_batch), after the clean-up and before the measurements, which then measure the expanded regions.
     measure: None; True: every result's `measurements` holds the geometry of its instances (measure.py), measured on the final label
     map; or a uint8 / uint16 [N, h, w, C] array or device tensor at the label maps' size: the intensity columns too.  One launch for
     all images of one output size."""
@@ -132,6 +135,9 @@ def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None
     if clean is not None:
         from . import components
         out = components.clean_instances_batch(out, **dict(clean))
+    if expand is not None:
+        from . import distance
+        out = distance.expand_instances_batch(out, expand)
     if measure is not None and measure is not False:
         from . import measure as _measure
         _measure.measure_instances_batch(out, None if measure is True else measure)

@@ -478,12 +478,14 @@ def assemble(plan, per_tile_preds, nms_thresh=0.5, device=None, stage=None, clea
 
 
 def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thresh=0.5, seg_thresh=0.5, max_workspace_bytes=None, stage=None,
-                  clean=None, measure=False):
+                  clean=None, measure=False, expand=None):
     """Instance segmentation of a whole image at native resolution -> TiledInstances.  image: host uint8 [H, W, 3] (uploaded once, to the
     model's device) or a device uint8 tensor; tile: the network input size, (th, tw) or one int, multiples of 32; overlap: pixels two
     neighbouring tiles share at least (choose it at least as large as the largest object: an object is cut at the edge of the tile that
     owns its centre); batch: tiles per predict call; clean: None, or a dict of components.clean's policy arguments (assemble);
-    measure: with True the result's `measurements` holds measure.measure_instances of the final (cleaned, if clean is given) label map
+    expand: None, or a distance in pixels (a number, at most 64): every instance of the STITCHED map is then grown by that much without
+    two instances merging (distance.expand_instances: no tile seams), after the clean-up and before the measurements;
+    measure: with True the result's `measurements` holds measure.measure_instances of the final (cleaned, expanded, if asked) label map
     against the uploaded uint8 image -- one more launch, one more upload (the jobs) and one more device -> host copy (the rows)."""
     import torch
     from . import inference
@@ -507,6 +509,9 @@ def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thres
     for a in range(0, len(pl), int(batch)):
         preds += inference.predict(model, x[a:a + int(batch)], nms_thresh, seg_thresh, None, max_workspace_bytes=max_workspace_bytes, packed=True)
     out = assemble(pl, preds, nms_thresh, dev, stage, clean)
+    if expand is not None:
+        from . import distance
+        out = distance.expand_instances(out, expand)
     if measure:
         from . import measure as _measure
         out.measurements = _measure.measure_instances(out, image)
