@@ -499,6 +499,34 @@ int kg_label_measure(const int* labels, int nimg, int H, int W, const void* imag
 int kg_label_distance(const int* labels, int nimg, int H, int W, int max_d2, int frame, int* d2, int* nearest, void* stream);
 int kg_label_regrow(const int* labels, int nimg, int H, int W, int max_d2, int frame, int op, int lo2, int hi2, int* out, void* stream);
 int kg_label_inscribed(const int* labels, const int* d2, int nimg, int H, int W, const int* jobs, int m, int* out, void* stream);
+/* Touching-neighbour graph (csrc/neighbours.hip; neighbours.py states the semantics in NumPy): which other instances an instance touches,
+ * and along how many pixel sides and corners.
+ * kg_label_neighbours: labels = device int32 [nimg][H][W], ANY int32 values (compared only); connectivity = 4 or 8; jobs = device int32
+ * [m][8] rows {img, id, y1, x1, y2, x2, resume, after} (half-open box), written by the caller -> out = device int64 [m][2 + 3 * slots] rows
+ * {count, more, (value, sides, corners) x slots}, 1 <= slots <= 64, every element written.  With P = the pixels of the box, clamped to the
+ * map, of image img with labels == id: for every p in P and each of the four side directions, the neighbour pixel, if it lies INSIDE THE
+ * MAP and holds a value v with v != id and v != 0, adds 1 to sides[v]; under connectivity 8 the four diagonal directions add to
+ * corners[v] by the same rule, under 4 corners is 0 and the diagonals are never read.  The neighbour set is {v : sides[v] + corners[v] >
+ * 0}.  Neighbours are read from the MAP, never from the box: a box edge or band edge inside the map is not an object edge, so the rows of
+ * bands that tile a box merge by value (sides and corners add) to the row of the box.  Values are compared only: INT_MIN, -1 and INT_MAX
+ * are ordinary neighbour values, and id may be any value, 0 included.
+ * The row lists the neighbour values in ASCENDING SIGNED ORDER, with resume != 0 only those > after (after is ignored when resume == 0);
+ * count = the slots filled (<= slots); more = 1 exactly when a further qualifying value exists beyond the last one written; unused slots
+ * are zeros.  A caller pages a long list by launching the job again with resume = 1 and after = the last value it got.
+ * A job whose image index lies outside [0, nimg), whose box is empty or inverted, or whose id the box does not hold gets a row of zeros
+ * and reads nothing else.
+ * SIZE RULE.  H, W <= 32768 as for kg_label_measure: a count stays below 2^33 and fits int64; nimg * H * W <= 2^31 - 1.
+ * INDEX RULE.  No value read from device memory becomes an index: the job table is the one device-read table, its box is clamped to the
+ * map before any address is formed, its image index is used only inside (unsigned)img < (unsigned)nimg, and resume / after are compared
+ * only; label values are compared and stored only; a neighbour outside the map is decided by a predicate on its coordinates before its
+ * address exists.  No atomics and no hash table: one workgroup per job extracts the values in order, the smallest qualifying value above
+ * a workgroup-uniform cursor per walk of the box, counting the previous one on the same walk -- at most slots + 1 walks per job, and the
+ * same row from run to run.
+ * One launch whatever m is; m == 0 is valid and launches nothing (jobs and out may then be NULL).  Validates on the host before any HIP
+ * call (null pointers, nimg, H, W > 0, the size rule, connectivity, slots, m >= 0, 4-byte alignment of labels and jobs, 8 of out) and
+ * never synchronises. */
+int kg_label_neighbours(const int* labels, int nimg, int H, int W, int connectivity, const int* jobs, int m, int slots, long long* out,
+                        void* stream);
 
 /* ---- per-box segmentation branch (KGnet.py:246-267, 321-350): ragged row bookkeeping ---- */
 int kg_seg_build_rows(const int* boxtab8, int nb, int* rowdesc, int* row2box, int* srcrow, void* stream);

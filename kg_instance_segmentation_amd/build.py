@@ -47,6 +47,7 @@ SOURCES = {
     "components.hip": [],
     "measure.hip": [],
     "distance.hip": [],
+    "neighbours.hip": [],
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function"]

@@ -119,7 +119,7 @@ def instances_from_predictions(preds):
 
 
 def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None, max_workspace_bytes=None, clean=None, measure=None,
-                      expand=None):
+                      expand=None, neighbours=None):
     """predict(packed=True) followed by the instance label map and the per-instance table of every image (instances.py), on the device:
     the label map (4 bytes per pixel) and the table (64 bytes per instance) replace n full-size masks as what crosses to the host.
     clean: None, or a dict of components.clean's policy arguments: every label map is then cleaned on the device (one components pass
@@ -128,7 +128,10 @@ def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None
     merging (distance.expand_instances_batch), after the clean-up and before the measurements, which then measure the expanded regions.
     measure: None; True: every result's `measurements` holds the geometry of its instances (measure.py), measured on the final label
     map; or a uint8 / uint16 [N, h, w, C] array or device tensor at the label maps' size: the intensity columns too.  One launch for
-    all images of one output size."""
+    all images of one output size.
+    neighbours: None; True, or a dict of neighbours.neighbours_instances' keyword arguments (connectivity, expand, slots,
+    max_job_pixels): every result's `neighbours` holds the touching-neighbour graph of its final label map (neighbours.py), one launch
+    for all images of one output size.  None adds no launch and no import."""
     if not torch.is_tensor(x) or x.device.type != "cuda":
         raise _lib.KGLibraryError("predict_instances (MI355X build) needs the input batch on a GPU device")
     out = instances_from_predictions(predict(model, x, nms_thresh, seg_thresh, image_sizes, max_workspace_bytes=max_workspace_bytes, packed=True))
@@ -141,6 +144,9 @@ def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None
     if measure is not None and measure is not False:
         from . import measure as _measure
         _measure.measure_instances_batch(out, None if measure is True else measure)
+    if neighbours is not None and neighbours is not False:
+        from . import neighbours as _neighbours
+        _neighbours.neighbours_instances_batch(out, **({} if neighbours is True else dict(neighbours)))
     return out
 
 

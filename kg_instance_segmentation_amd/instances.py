@@ -26,12 +26,14 @@ TABLE_COLUMNS = ("area_full", "area_visible", "y1", "x1", "y2", "x2", "sum_y", "
 
 class Instances:
     """One image's result of inference.predict_instances: labels = device int32 [h, w]; dets = float32 [n, 5], predict's; table = host
-    int64 [n, 8] (TABLE_COLUMNS); masks = the BitMasks; measurements = None unless asked for (measure=, measure.py: a Measurements)."""
-    __slots__ = ("labels", "dets", "table", "masks", "measurements")
+    int64 [n, 8] (TABLE_COLUMNS); masks = the BitMasks; measurements = None unless asked for (measure=, measure.py: a Measurements);
+    neighbours = None unless asked for (neighbours=, neighbours.py: a Neighbours)."""
+    __slots__ = ("labels", "dets", "table", "masks", "measurements", "neighbours")
 
     def __init__(self, labels, dets, table, masks):
         self.labels, self.dets, self.table, self.masks = labels, dets, table, masks
         self.measurements = None
+        self.neighbours = None
 
     def __len__(self):
         return len(self.dets)

@@ -478,7 +478,7 @@ def assemble(plan, per_tile_preds, nms_thresh=0.5, device=None, stage=None, clea
 
 
 def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thresh=0.5, seg_thresh=0.5, max_workspace_bytes=None, stage=None,
-                  clean=None, measure=False, expand=None):
+                  clean=None, measure=False, expand=None, neighbours=None):
     """Instance segmentation of a whole image at native resolution -> TiledInstances.  image: host uint8 [H, W, 3] (uploaded once, to the
     model's device) or a device uint8 tensor; tile: the network input size, (th, tw) or one int, multiples of 32; overlap: pixels two
     neighbouring tiles share at least (choose it at least as large as the largest object: an object is cut at the edge of the tile that
@@ -486,7 +486,10 @@ def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thres
     expand: None, or a distance in pixels (a number, at most 64): every instance of the STITCHED map is then grown by that much without
     two instances merging (distance.expand_instances: no tile seams), after the clean-up and before the measurements;
     measure: with True the result's `measurements` holds measure.measure_instances of the final (cleaned, expanded, if asked) label map
-    against the uploaded uint8 image -- one more launch, one more upload (the jobs) and one more device -> host copy (the rows)."""
+    against the uploaded uint8 image -- one more launch, one more upload (the jobs) and one more device -> host copy (the rows);
+    neighbours: None; True, or a dict of neighbours.neighbours_instances' keyword arguments (connectivity, expand, slots,
+    max_job_pixels): the result's `neighbours` then holds the touching-neighbour graph of the final label map (neighbours.py) -- one more
+    launch, upload and copy back per round of paging.  None adds no launch and no import."""
     import torch
     from . import inference
     if int(batch) < 1:
@@ -515,4 +518,7 @@ def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thres
     if measure:
         from . import measure as _measure
         out.measurements = _measure.measure_instances(out, image)
+    if neighbours is not None and neighbours is not False:
+        from . import neighbours as _neighbours
+        out.neighbours = _neighbours.neighbours_instances(out, **({} if neighbours is True else dict(neighbours)))
     return out
