@@ -527,6 +527,45 @@ int kg_label_inscribed(const int* labels, const int* d2, int nimg, int H, int W,
  * never synchronises. */
 int kg_label_neighbours(const int* labels, int nimg, int H, int W, int connectivity, const int* jobs, int m, int slots, long long* out,
                         void* stream);
+/* Run-length lists (csrc/runlengths.hip; runlengths.py states the semantics in NumPy): the Kaggle rows and COCO counts of every instance
+ * of a label map, and the way back from run-length rows to a label map.
+ * PIXEL ORDER.  p = x * H + y: down the columns first, then left to right, 0-based (Kaggle's EncodedPixels numbers the same order from 1).
+ * JOB.  {img, id, y1, x1, y2, x2}, the layout of kg_label_measure: a half-open box, clamped to the map before any address is formed.
+ * P = the pixels of the clamped box in image img with labels == id.  Values are compared only, so id may be any int32, 0, INT_MIN and
+ * INT_MAX included.  A job whose image index lies outside [0, nimg), whose box is empty or inverted, or whose id the box does not hold
+ * produces nothing.
+ * HEAD AND TAIL.  A pixel of P is a head when p == 0 or the map's pixel at p - 1 does not hold id; a tail when p == H * W - 1 or the
+ * pixel at p + 1 does not hold id.  The pixel at p - 1 is (y - 1, x), or (H - 1, x - 1) when y == 0; the pixel at p + 1 is (y + 1, x), or
+ * (0, x + 1) when y == H - 1.  Both are read from the MAP, never from the box, and a position outside the map is decided by a predicate
+ * on its coordinates before its address exists.  A run therefore continues from the bottom of one column into the top of the next: the
+ * 4 x 3 map with id at p = 2, 3, 4, 5, 7, 8 has the runs {2, 5} and {7, 8}, Kaggle's "3 4 8 2".
+ * RUNS.  The k-th head and the k-th tail of a job in ascending p delimit its k-th run {first, last}, 0-based and inclusive; Kaggle's pair
+ * is (first + 1, last - first + 1).  Because the neighbours come from the map, the heads and the tails of column bands that tile a box,
+ * taken in ascending x, concatenate to the box's; a band can hold a head whose tail lies in a later band, so the two are counted and
+ * offset separately.
+ * kg_label_run_counts: labels = device int32 [nimg][H][W]; jobs = device int32 [m][6], written by the caller -> out = device int32 [m][2]
+ * rows {heads, tails}, every element written.
+ * kg_label_runs: jobs = device int32 [m][8] rows {img, id, y1, x1, y2, x2, head_at, tail_at} -> out = device int32 [R][2].  The k-th head
+ * of a job stores its p into out[head_at + k][0], the k-th tail into out[tail_at + k][1], each only inside the 64-bit unsigned predicate
+ * (head_at + k) < R (tail_at + k for a tail): a negative or oversized offset from a wrong table never leaves the buffer.  With a table
+ * built from kg_label_run_counts (exclusive prefix sums of heads and of tails, R = their total) every element of out is written;
+ * nothing else is touched.
+ * kg_runs_paint: runs = device int32 [R][3] rows {first, last, value}, SORTED by first and DISJOINT -- the caller's promise, the entry
+ * cannot check it -> out = device int32 [H][W], every element written: value where first <= p <= last for a row, else background.  One
+ * lane per output pixel in row-major order; the row is found by a binary search over `first` whose loop bound derives from R.
+ * R == 0 is valid (runs may then be NULL).
+ * SIZE RULE.  H, W <= 32768 as for kg_label_measure; nimg * H * W <= 2^31 - 1 (H * W for kg_runs_paint), so p fits int32.
+ * INDEX RULE.  The job table is the one device-read table: its box is clamped to the map before any address is formed and its image
+ * index is used only inside (unsigned)img < (unsigned)nimg; label values are compared only.  The store of kg_label_runs is the family's
+ * one exception: its slot is an offset of the table plus a PREFIX COUNT OF PREDICATES (not a label value), bounded by the predicate
+ * above where it is made.  kg_runs_paint reads row i only for a search position i in [0, R); first, last and value are compared and
+ * stored only.  No atomics.
+ * One launch whatever m is (one workgroup per job); m == 0 launches nothing (jobs and out may then be NULL), and so does R == 0 for
+ * kg_label_runs.  All three validate on the host before any HIP call (null pointers, nimg, H, W > 0, the size rule, m, R >= 0, 4-byte
+ * alignment, out not overlapping labels / runs) and never synchronise. */
+int kg_label_run_counts(const int* labels, int nimg, int H, int W, const int* jobs, int m, int* out, void* stream);
+int kg_label_runs(const int* labels, int nimg, int H, int W, const int* jobs, int m, int* out, int R, void* stream);
+int kg_runs_paint(const int* runs, int R, int H, int W, int background, int* out, void* stream);
 
 /* ---- per-box segmentation branch (KGnet.py:246-267, 321-350): ragged row bookkeeping ---- */
 int kg_seg_build_rows(const int* boxtab8, int nb, int* rowdesc, int* row2box, int* srcrow, void* stream);

@@ -1,5 +1,5 @@
-"""The argument layer the label-map modules share (instances, tiling, labelmetrics, components, measure): label maps and job tables,
-host or device.  fn is the public function the message names."""
+"""The argument layer the label-map modules share (instances, tiling, labelmetrics, components, measure, neighbours, runlengths): label maps
+and job tables, host or device.  fn is the public function the message names."""
 import numpy as np
 
 from . import _lib
@@ -71,3 +71,14 @@ def device_jobs(fn, jobs, ncol, names, dev, rows="m", owner="maps'"):
             raise KGLibraryError(f"{fn}: device jobs must be int32 [{rows}, {ncol}] on the {owner} device")
         return jobs.contiguous()
     return upload_jobs(host_jobs(fn, jobs, ncol, names, rows), dev)
+
+
+def instance_jobs(inst, img, grow, H, W):
+    """int64 [n, 6]: ids 1 .. n of image img, boxes from the table grown by `grow` and clamped; an instance with no visible pixel gets an
+    empty box, hence an empty row."""
+    t = np.asarray(inst.table, np.int64).reshape(-1, 8)
+    n = len(t)
+    box = t[:, 2:6] + [-grow, -grow, grow, grow]
+    box[:, :2] = np.clip(box[:, :2], 0, [H, W]); box[:, 2:] = np.clip(box[:, 2:], 0, [H, W])
+    box = np.where(t[:, 1:2] > 0, box, 0)
+    return np.concatenate([np.full((n, 1), int(img)), np.arange(1, n + 1)[:, None], box], 1).astype(np.int64).reshape(-1, 6)

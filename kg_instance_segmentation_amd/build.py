@@ -48,6 +48,7 @@ SOURCES = {
     "measure.hip": [],
     "distance.hip": [],
     "neighbours.hip": [],
+    "runlengths.hip": [],
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function"]

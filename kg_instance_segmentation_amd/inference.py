@@ -119,7 +119,7 @@ def instances_from_predictions(preds):
 
 
 def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None, max_workspace_bytes=None, clean=None, measure=None,
-                      expand=None, neighbours=None):
+                      expand=None, neighbours=None, runs=None):
     """predict(packed=True) followed by the instance label map and the per-instance table of every image (instances.py), on the device:
     the label map (4 bytes per pixel) and the table (64 bytes per instance) replace n full-size masks as what crosses to the host.
     clean: None, or a dict of components.clean's policy arguments: every label map is then cleaned on the device (one components pass
@@ -131,7 +131,10 @@ def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None
     all images of one output size.
     neighbours: None; True, or a dict of neighbours.neighbours_instances' keyword arguments (connectivity, expand, slots,
     max_job_pixels): every result's `neighbours` holds the touching-neighbour graph of its final label map (neighbours.py), one launch
-    for all images of one output size.  None adds no launch and no import."""
+    for all images of one output size.  None adds no launch and no import.
+    runs: None; True, or a dict of runlengths.runs_instances' keyword arguments (max_job_pixels): every result's `runs` holds the
+    run-length lists of its instances (runlengths.py: Kaggle rows, COCO counts), taken last, on the final label map -- two launches and
+    two copies back for all images of one output size.  None adds no launch and no import."""
     if not torch.is_tensor(x) or x.device.type != "cuda":
         raise _lib.KGLibraryError("predict_instances (MI355X build) needs the input batch on a GPU device")
     out = instances_from_predictions(predict(model, x, nms_thresh, seg_thresh, image_sizes, max_workspace_bytes=max_workspace_bytes, packed=True))
@@ -147,6 +150,9 @@ def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None
     if neighbours is not None and neighbours is not False:
         from . import neighbours as _neighbours
         _neighbours.neighbours_instances_batch(out, **({} if neighbours is True else dict(neighbours)))
+    if runs is not None and runs is not False:
+        from . import runlengths
+        runlengths.runs_instances_batch(out, **({} if runs is True else dict(runs)))
     return out
 
 

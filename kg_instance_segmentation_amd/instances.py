@@ -5,7 +5,8 @@ predict() ends where the reference's post_processing ends: n full-size binary ma
 them -- counts, areas, centroids, boxes, a non-overlapping submission -- comes from ONE label map per image: every pixel holds the id
 of the instance it belongs to, overlaps resolved.  label_map / overlay run on the device from the words (csrc/instances.hip); the *_host
 functions state the same semantics in NumPy over dense [n, H, W] arrays (the CPU route, and the yardstick of the GPU tests); run-length
-encoding is host NumPy over a label map copied back.
+encoding here is host NumPy over a label map copied back (runlengths.py lists the runs on the device, with these functions as its
+yardstick).
 
 Semantics (include/kgnet_hip.h, kg_instance_labels / kg_instance_overlay):
   label map   0 where no mask of the image covers the pixel, else the id of the first covering row in priority order.  Priority order is
@@ -27,13 +28,15 @@ TABLE_COLUMNS = ("area_full", "area_visible", "y1", "x1", "y2", "x2", "sum_y", "
 class Instances:
     """One image's result of inference.predict_instances: labels = device int32 [h, w]; dets = float32 [n, 5], predict's; table = host
     int64 [n, 8] (TABLE_COLUMNS); masks = the BitMasks; measurements = None unless asked for (measure=, measure.py: a Measurements);
-    neighbours = None unless asked for (neighbours=, neighbours.py: a Neighbours)."""
-    __slots__ = ("labels", "dets", "table", "masks", "measurements", "neighbours")
+    neighbours = None unless asked for (neighbours=, neighbours.py: a Neighbours); runs = None unless asked for (runs=, runlengths.py: a
+    RunLengths)."""
+    __slots__ = ("labels", "dets", "table", "masks", "measurements", "neighbours", "runs")
 
     def __init__(self, labels, dets, table, masks):
         self.labels, self.dets, self.table, self.masks = labels, dets, table, masks
         self.measurements = None
         self.neighbours = None
+        self.runs = None
 
     def __len__(self):
         return len(self.dets)

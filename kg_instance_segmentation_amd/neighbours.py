@@ -34,7 +34,7 @@ import math
 import numpy as np
 
 from . import _lib, _labelmaps, labelmetrics
-from ._labelmaps import is_device
+from ._labelmaps import instance_jobs as _instance_jobs, is_device
 from .labelmetrics import split_jobs
 
 KGLibraryError = _lib.KGLibraryError
@@ -286,17 +286,6 @@ def neighbours(labels, n=None, jobs=None, stats=None, connectivity=4, slots=16, 
 
 
 # ---- Instances ----------------------------------------------------------------------------------------------------------------------------
-
-def _instance_jobs(inst, img, grow, H, W):
-    """int64 [n, 6]: ids 1 .. n of image img, boxes from the table grown by `grow` and clamped; an instance with no visible pixel gets an
-    empty box, hence an empty row."""
-    t = np.asarray(inst.table, np.int64).reshape(-1, 8)
-    n = len(t)
-    box = t[:, 2:6] + [-grow, -grow, grow, grow]
-    box[:, :2] = np.clip(box[:, :2], 0, [H, W]); box[:, 2:] = np.clip(box[:, 2:], 0, [H, W])
-    box = np.where(t[:, 1:2] > 0, box, 0)
-    return np.concatenate([np.full((n, 1), int(img)), np.arange(1, n + 1)[:, None], box], 1).astype(np.int64).reshape(-1, 6)
-
 
 def _instance_graphs(insts, connectivity, expand, slots, max_job_pixels):
     """-> one Neighbours per entry (None for a None entry); the entries themselves are not touched"""
