@@ -566,6 +566,54 @@ int kg_label_neighbours(const int* labels, int nimg, int H, int W, int connectiv
 int kg_label_run_counts(const int* labels, int nimg, int H, int W, const int* jobs, int m, int* out, void* stream);
 int kg_label_runs(const int* labels, int nimg, int H, int W, const int* jobs, int m, int* out, int R, void* stream);
 int kg_runs_paint(const int* runs, int R, int H, int W, int background, int* out, void* stream);
+/* Instance outlines (csrc/contours.hip; contours.py states the semantics in NumPy as contours_host): the outline of every instance of a
+ * label map as polygon rings, exact in integers.
+ * JOB.  {img, id, y1, x1, y2, x2}, a half-open box clamped to the map.  P = the pixels of the clamped box in image img with labels == id.
+ * Everything else is non-P, the same id outside the box included: the polygon of P is self-contained in the box.  Values are compared
+ * only: 0, -1, INT_MIN and INT_MAX are ordinary ids.  H, W <= 32768 as for kg_label_measure.
+ * LATTICE.  Vertices are (Y, X) with 0 <= Y <= H and 0 <= X <= W; pixel (y, x) is the square between vertices (y, x) and (y + 1, x + 1).
+ * CRACKS.  A directed crack leaves a vertex in one of four directions, E (x + 1) = 0, S (y + 1) = 1, W (x - 1) = 2, N (y - 1) = 3.  It
+ * exists when P is on its right-hand side and non-P on its left.  With m(y, x) = "the pixel is in P" (false outside the box):
+ *     E at (Y, X) iff m(Y, X) && !m(Y - 1, X)              (the top edge of a P pixel)
+ *     S at (Y, X) iff m(Y, X - 1) && !m(Y, X)              (the right edge)
+ *     W at (Y, X) iff m(Y - 1, X - 1) && !m(Y, X - 1)      (the bottom edge)
+ *     N at (Y, X) iff m(Y - 1, X) && !m(Y - 1, X - 1)      (the left edge)
+ * SUCCESSOR.  A crack with direction d arrives at vertex V; its successor is the first existing crack leaving V in the order right turn
+ * (d + 1) & 3, straight d, left turn (d + 3) & 3.  One always exists.  Right first makes P 4-connected: two pixels that meet only at a
+ * corner get separate rings.  8-connectivity is out of scope.
+ * RINGS.  The cracks fall into disjoint cycles, the rings.  The vertices of a ring are the vertices where the direction changes.  An
+ * outer boundary runs clockwise on the screen and has positive shoelace area; a hole runs the other way and has negative area.  A ring
+ * may visit a vertex twice (a diagonal pinch); it never repeats a crack.
+ * START.  A candidate is an E crack at (Y, X) with no E crack at (Y, X - 1): the start of a maximal run of top edges.  Every ring holds
+ * at least one candidate, and a candidate vertex is always a corner.  The start of a ring is its candidate with the smallest (Y, X) in
+ * raster order; the vertex list begins with that vertex and follows the traversal; the closing vertex is not repeated.
+ * ORDER.  The rings of a job are ordered by start (Y, X) in raster order; starts are distinct.
+ * PER RING.  count = the number of vertices (even, at least 4); perimeter = the number of cracks; area2 = the sum over the vertices of
+ * x_i * y_(i+1) - x_(i+1) * y_i, a signed int64 (twice the shoelace area).  Coordinates are absolute map coordinates (Y, X), int32.
+ * BAD JOBS.  An image index outside [0, nimg), an empty or inverted box, an id the box does not hold: zero rings.
+ * SIZE.  A job is traced on the device when its bitmap fits 32 KiB of LDS: with h, w the clamped box,
+ * (h + 2) * 32 * (ceil((w + 2) / 32) | 1) <= 2^18 -- one zero halo on each side and a row pitch of an odd number of dwords.  A job that
+ * does not fit gets status = 1 and zero counts from kg_label_contour_counts and writes nothing in kg_label_contours; polygons cannot be
+ * banded, so contours.py traces such a job on the host.
+ * kg_label_contour_counts: labels = device int32 [nimg][H][W]; jobs = device int32 [m][6], written by the caller -> out = device int64
+ * [m][4] rows {rings, vertices, perimeter, status}, every element written.
+ * kg_label_contours: jobs = device int32 [m][8] rows {img, id, y1, x1, y2, x2, ring_at, vert_at} -> rings = device int64 [R][4] rows
+ * {first, count, perimeter, area2}, verts = device int32 [V][2] rows (y, x).  The k-th ring of a job goes to row ring_at + k only inside
+ * the 64-bit unsigned predicate (ring_at + k) < R; its first is vert_at plus the vertex counts of the job's rings before it, and its i-th
+ * vertex goes to verts[first + i] only inside (first + i) < V: a negative or oversized offset from a wrong table never leaves the
+ * buffers.  With a table built from kg_label_contour_counts (exclusive prefix sums of rings and of vertices, R and V their totals) every
+ * element of both is written; nothing else is touched.
+ * INDEX RULE.  The job table is the one device-read table: box clamped before any address is formed, image index only inside
+ * (unsigned)img < (unsigned)nimg; label values are compared only.  The family's one new exception: the tracer's position is an LDS bit
+ * index that depends on bits derived from labels; it is bounded by construction (a crack touches a P pixel of the box) and by an explicit
+ * clamp.  No global address depends on a label; global stores depend only on the job table plus prefix counts, inside the range
+ * predicates.  No atomics.
+ * One launch whatever m is (one workgroup per job); m == 0 launches nothing (jobs and out may then be NULL), and so does R == V == 0 for
+ * kg_label_contours.  Both validate on the host before any HIP call (null pointers, nimg, H, W > 0, the size rules, m, R, V >= 0,
+ * alignment -- 4 bytes, 8 for the int64 rows --, outputs not overlapping labels or each other) and never synchronise. */
+int kg_label_contour_counts(const int* labels, int nimg, int H, int W, const int* jobs, int m, long long* out, void* stream);
+int kg_label_contours(const int* labels, int nimg, int H, int W, const int* jobs, int m, long long* rings, int R, int* verts, int V,
+                      void* stream);
 
 /* ---- per-box segmentation branch (KGnet.py:246-267, 321-350): ragged row bookkeeping ---- */
 int kg_seg_build_rows(const int* boxtab8, int nb, int* rowdesc, int* row2box, int* srcrow, void* stream);

@@ -49,6 +49,7 @@ SOURCES = {
     "distance.hip": [],
     "neighbours.hip": [],
     "runlengths.hip": [],
+    "contours.hip": [],
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function"]

@@ -5,7 +5,7 @@
 //
 // INDEX RULE of the family.  Every entry validates on the host before any HIP call and never synchronises; the number of launches does
 // not depend on a count read from the device; every output element is written.  No address in a kernel depends on a value read from
-// device memory, with three kinds of exception, each bounded where it is made:
+// device memory, with four kinds of exception, each bounded where it is made:
 //   - a job table (a device table the caller wrote): its box is clamped to the map BEFORE any address is formed (kg_job_box), and any
 //     other index it carries is used only inside an unsigned range predicate that empties the box when it fails, so even a wrong table
 //     cannot make a kernel leave its buffers;
@@ -13,7 +13,11 @@
 //     components.hip, the index is formed only inside (unsigned)(v - 1) < (unsigned)n;
 //   - the run slot of kg_label_runs (runlengths.hip): an offset of the job table plus a prefix count of predicates -- not a label value --
 //     and the store happens only inside the 64-bit unsigned predicate slot < R.  (kg_runs_paint reads a row only at a binary-search
-//     position in [0, R).)
+//     position in [0, R).)  kg_label_contours (contours.hip) stores the same way: ring slot and vertex offset are offsets of the job
+//     table plus prefix counts, inside slot < R and first + k < V;
+//   - the tracer of contours.hip: its position is an LDS bit index that depends on bits derived from labels.  It is bounded by
+//     construction (a crack touches a P pixel of the box) and by an explicit clamp to [0, h] x [0, w] after every step.  No GLOBAL
+//     address depends on a label there either.
 // Labels and pixel values are otherwise predicates, summands and stored values only.
 #pragma once
 #include "kg_common.h"
