@@ -614,6 +614,55 @@ int kg_runs_paint(const int* runs, int R, int H, int W, int background, int* out
 int kg_label_contour_counts(const int* labels, int nimg, int H, int W, const int* jobs, int m, long long* out, void* stream);
 int kg_label_contours(const int* labels, int nimg, int H, int W, const int* jobs, int m, long long* rings, int R, int* verts, int V,
                       void* stream);
+/* Polygon annotations to a label map (csrc/polygons.hip; polygons.py states the rule in NumPy as fill_host): the exact tiled polygon
+ * fill, the inverse of the outlines above.  The fill rule is stated in integers, so the device, the host statement and any other
+ * implementation agree on every pixel.
+ * LATTICE.  The lattice is that of the outlines.  Pixel (y, x) is the square between vertices (x, y) and (x + 1, y + 1).  Its centre is
+ * (x + 0.5, y + 0.5).
+ * FIXED POINT.  F = 256.  The host turns a float64 vertex into integers by q = rint(v * 256) (round-half-even).  It rejects non-finite
+ * values and |q| > 2^29 (about 2 M pixels).  Every coordinate difference then fits int32.  Every product below is a 32 x 32 -> 64 bit
+ * multiply; no 64 x 64 multiply is needed.  A pixel centre is (256 x + 128, 256 y + 128).
+ * EDGES.  Every ring contributes its edges, the closing one included, each ordered upward as (x0, y0, x1, y1) with y0 < y1.
+ * Horizontal edges are dropped.  The host builds one int32 [E][4] table.  A ring that repeats its first vertex (GeoJSON) therefore
+ * costs nothing.  A ring of one or two vertices covers nothing.
+ * CROSSING.  An edge counts for a centre (cx, cy) iff
+ *     y0 <= cy < y1  and  (x1 - x0) * (cy - y0) > (cx - x0) * (y1 - y0)      (int64)
+ * That is, its intersection with the scanline lies strictly right of the centre.
+ * PART.  A part is a list of rings.  It covers a pixel iff the number of counting edges over all its rings is odd (even-odd).  Holes,
+ * islands in holes and self-intersections need no orientation.
+ * ROW.  A row is a list of parts with one int32 value.  It covers a pixel iff any of its parts does (union).  This follows COCO's
+ * several polygons per object and GeoJSON's MultiPolygon.
+ * MAP.  out[y, x] is the value of the first row, in row order, that covers the pixel, else background.  top = "last" reverses the row
+ * order; painter's order is what annotation tools draw.  cover[y, x] (optional) is the number of rows that cover the pixel, each row
+ * counted once however many of its parts do.
+ * CONSEQUENCES.  Top-left inclusive and watertight: a centre exactly on a left or top edge is inside, on a right or bottom edge it is
+ * outside, and polygons that share edges give every pixel to exactly one of them.  The rings of the outlines above have integer
+ * vertices, so no centre lies on an edge, and filling the outlines of a label map gives the map back exactly on the traced ids.
+ * TABLES.  The map is cut into tiles of KG_POLY_TILE_H x KG_POLY_TILE_W pixels, tiles_y = ceil(H / KG_POLY_TILE_H) rows of tiles_x =
+ * ceil(W / KG_POLY_TILE_W); tile t of the stack is (img * tiles_y + ty) * tiles_x + tx.  items = device int32 [n_items][4] rows {value,
+ * edge_first, edge_count, row}, one per (tile, part): the part's edges are edges[edge_first .. edge_first + edge_count).  tile_ptr =
+ * device int32 [nimg * tiles_y * tiles_x + 1]: tile t walks items[tile_ptr[t] .. tile_ptr[t + 1]) in list order.  For a pixel of tile t
+ * an item covers the pixel iff the number of its counting edges is odd; out = the value of the first covering item of the list, else
+ * background; cover = the number of covering items whose row differs from the row of the covering item counted before it for that pixel.
+ * With the lists polygons.tile_lists builds -- every part in every tile its box meets, in row order, reversed for top = "last" -- this is
+ * the MAP rule.  Every element of out (and of cover) is written, an empty tile with background (and 0).  One workgroup per tile stages
+ * the edges of an item in LDS in chunks of KG_POLY_EDGE_CHUNK; the result does not depend on the chunking.
+ * SIZE RULE.  H, W <= 32768 as for kg_label_measure; nimg * H * W <= 2^31 - 1; E, n_items are int32.
+ * INDEX RULE.  Two levels of caller-written tables, the family's one new exception.  tile_ptr[t] and tile_ptr[t + 1] are used only
+ * as a range clamped inside [0, n_items]; a decreasing pair is an empty range.  An item's edge_first, edge_count are used only inside
+ * the 64-bit unsigned predicates edge_first <= E and edge_count <= E - edge_first (a negative number is a huge unsigned one); a failing
+ * predicate empties the item.  No address depends on an edge coordinate, a value or a row.  A wrong table can therefore produce wrong
+ * pixels, but it cannot reach outside edges, items, out or cover.  Coordinate differences of an edge table outside the fixed-point
+ * range wrap modulo 2^32.  A gather: each pixel is written once by one lane, no atomics, no dependence on the order workgroups run in.
+ * ONE launch whatever the sizes are (the grid strides over the tiles); E == 0 or n_items == 0 is valid (edges / items may then be NULL).
+ * cover may be NULL.  Validates on the host before any HIP call (sizes, the size rule, null pointers, alignment -- 16 bytes for edges and
+ * items, whose rows are read whole, 4 bytes for the rest --, out and cover not overlapping each other or a table) and never
+ * synchronises. */
+#define KG_POLY_TILE_H 32
+#define KG_POLY_TILE_W 64
+#define KG_POLY_EDGE_CHUNK 256
+int kg_polygons_fill(const int* edges, int E, const int* items, int n_items, const int* tile_ptr, int nimg, int H, int W, int background,
+                     int* out, int* cover, void* stream);
 
 /* ---- per-box segmentation branch (KGnet.py:246-267, 321-350): ragged row bookkeeping ---- */
 int kg_seg_build_rows(const int* boxtab8, int nb, int* rowdesc, int* row2box, int* srcrow, void* stream);

@@ -50,6 +50,7 @@ SOURCES = {
     "neighbours.hip": [],
     "runlengths.hip": [],
     "contours.hip": [],
+    "polygons.hip": [],
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function"]

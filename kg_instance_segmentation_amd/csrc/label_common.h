@@ -5,7 +5,7 @@
 //
 // INDEX RULE of the family.  Every entry validates on the host before any HIP call and never synchronises; the number of launches does
 // not depend on a count read from the device; every output element is written.  No address in a kernel depends on a value read from
-// device memory, with four kinds of exception, each bounded where it is made:
+// device memory, with five kinds of exception, each bounded where it is made:
 //   - a job table (a device table the caller wrote): its box is clamped to the map BEFORE any address is formed (kg_job_box), and any
 //     other index it carries is used only inside an unsigned range predicate that empties the box when it fails, so even a wrong table
 //     cannot make a kernel leave its buffers;
@@ -17,7 +17,11 @@
 //     table plus prefix counts, inside slot < R and first + k < V;
 //   - the tracer of contours.hip: its position is an LDS bit index that depends on bits derived from labels.  It is bounded by
 //     construction (a crack touches a P pixel of the box) and by an explicit clamp to [0, h] x [0, w] after every step.  No GLOBAL
-//     address depends on a label there either.
+//     address depends on a label there either;
+//   - the two table levels of kg_polygons_fill (polygons.hip), both written by the caller: tile_ptr[t], tile_ptr[t + 1] are used only as a
+//     range clamped inside [0, n_items] (a decreasing pair is an empty range), and an item's edge_first, edge_count only inside the 64-bit
+//     unsigned predicates first <= E and count <= E - first, which empty the item when they fail.  No address depends on an edge
+//     coordinate, a value or a row: a wrong table gives wrong pixels and cannot reach outside edges, items, out or cover.
 // Labels and pixel values are otherwise predicates, summands and stored values only.
 #pragma once
 #include "kg_common.h"

@@ -23,7 +23,7 @@ Semantics
   iou         I / (A_p + A_g - I) in float64; a pair that does not meet has 0."""
 import numpy as np
 
-from . import _lib, evaluation, instances
+from . import _lib, evaluation, instances, polygons
 from ._labelmaps import device_jobs, device_maps, host_maps, is_device
 from .bitmasks import BitMasks, unpack_host
 
@@ -332,7 +332,9 @@ class LabelEvaluator:
     def add(self, pred, gt, conf=None):
         """pred: an Instances / TiledInstances (its label map, its table as the stats, its dets' confidences), or a (labels, n_pred) pair,
         for which conf [n_pred] is needed for the AP part (without it seg_ap / seg_iou do not see the image).
-        gt: a (labels, n_gt) pair, host or device; a BitMasks; or dense [ng, H, W] masks (NumPy or tensor).  The two mask forms become a
+        gt: a (labels, n_gt) pair, host or device; a BitMasks; dense [ng, H, W] masks (NumPy or tensor); or a polygons.Polygons, which is
+        filled at the prediction's size with the ids 1 .. m (polygons.fill on the prediction's device, fill_host for a host prediction: the
+        first row wins a pixel, n_gt = m).  The two mask forms become a
         label map and its stats through instances.label_map(with_table=True): where GT masks overlap, the FIRST row wins the pixel, and a
         GT row wholly hidden that way has area 0 and is not counted in G.
         A device predicted map is scored on the device (contingency), a host one through contingency_host.  Returns the Contingency."""
@@ -350,6 +352,10 @@ class LabelEvaluator:
         if torch.is_tensor(plab) and not on_device:
             plab = plab.numpy()
         shape = tuple(plab.shape)
+        if isinstance(gt, polygons.Polygons):                         # filled at the prediction's size, where the prediction lives
+            if len(shape) != 2:
+                raise KGLibraryError(f"LabelEvaluator.add: a predicted map of {shape} against polygons")
+            gt = (polygons.fill(gt, *shape, plab.device) if on_device else polygons.fill_host(gt, *shape), len(gt))
         if on_device:
             glab, n_gt, gt_stats = self._device_gt(gt, plab.device)
             if tuple(glab.shape) != shape:
