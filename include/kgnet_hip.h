@@ -663,6 +663,54 @@ int kg_label_contours(const int* labels, int nimg, int H, int W, const int* jobs
 #define KG_POLY_EDGE_CHUNK 256
 int kg_polygons_fill(const int* edges, int E, const int* items, int n_items, const int* tile_ptr, int nimg, int H, int W, int background,
                      int* out, int* cover, void* stream);
+/* Convex hulls (csrc/hulls.hip; hulls.py states the semantics in NumPy / Python integers as hulls_host): the convex hull of every
+ * instance of a label map and the descriptors that are functions of it -- convex area (solidity), maximum and minimum Feret diameter,
+ * hull perimeter (convexity) -- exact in integers.
+ * JOB.  {img, id, y1, x1, y2, x2}, a half-open box clamped to the map.  P = the pixels of the clamped box in image img with labels == id.
+ * Values are compared only: 0, -1, INT_MIN and INT_MAX are ordinary ids.  H, W <= 32768 as for kg_label_measure.
+ * LATTICE.  As for the outlines: pixel (y, x) is the square between vertices (y, x) and (y + 1, x + 1).  C(P) is the set of the four
+ * corners of every pixel of P.
+ * HULL.  The convex hull of C(P), as the ring of its STRICT vertices: no vertex lies on the segment between its neighbours.
+ * RING ORDER.  The ring runs clockwise on the screen: area2 = the sum over the vertices of x_i * y_(i+1) - x_(i+1) * y_i is positive, the
+ * sign of an outer ring of the outlines.  It starts at the vertex with the smallest (Y, X) in raster order; the closing vertex is not
+ * repeated.  Coordinates are absolute map coordinates (Y, X), int32.
+ * EXTENT FORM.  For a lattice line Y let L(Y) be the smallest and R(Y) the largest X of a corner of C(P) on that line; both are defined
+ * where pixel row Y - 1 or Y of the box holds a pixel of P.  The ring is, in this order: (top, L(top)); the vertices of the upper concave
+ * envelope of R from top to bottom; the vertices of the lower convex envelope of L from bottom to top, excluding the start.  (Y_i, F_i)
+ * is a strict envelope vertex iff for all defined j < i < k
+ *     (Y_i - Y_j)(F_k - F_i) - (Y_k - Y_i)(F_i - F_j) > 0 for L, < 0 for R;
+ * equivalently the largest slope to a defined line before it is strictly below the smallest slope to a defined line after it (above
+ * and the largest, for R), both rationals compared by cross-multiplication in int64.  The first and last defined lines always give
+ * vertices.  The extent form equals Andrew's monotone chain over C(P) with the start and sign above (tests/test_hulls_cpu.py).
+ * ROW.  int64 [10] = {area, count, area2, feret_max2, fmax_i, fmax_j, minw_num, minw_den2, minw_edge, status}.  area = |P|.  count is the
+ * number of ring vertices, even or odd, at least 4.  area2 is twice the hull's area.  feret_max2 is the largest squared distance
+ * between two ring vertices and (fmax_i, fmax_j), i < j, the ring indices of that pair; a tie goes to the lexicographically smallest
+ * pair.  For edge k (ring vertex k to k + 1, cyclic) c_k = the maximum over the ring vertices u of |cross(v_(k+1) - v_k, u - v_k)| and
+ * d_k = |v_(k+1) - v_k|^2.  The minimum caliper width squared is the minimum over k of c_k^2 / d_k; minw_num = c_k, minw_den2 = d_k and
+ * minw_edge = k of that minimum.  Edges are compared exactly, c_a^2 d_b < c_b^2 d_a, a tie to the smallest k.  With coordinates up to
+ * 32768 these products reach 2^93: the comparison is made in 128 bits (two 64 x 64 -> 128 bit products) on the device and in Python
+ * integers on the host, never in int64 or float.
+ * STATUS.  0 = ok.  1 = the clamped box has more than 4095 rows, the device limit (4096 lattice lines of L and R in 32 KiB of LDS): the
+ * row is zero and nothing is stored; hulls.py never produces it, see BANDS.  2 = count > cap: the statistics are right and only the first
+ * cap vertices are stored.
+ * BAD JOBS.  An image index outside [0, nimg), an empty or inverted box, an id the box does not hold: a row of zeros, no vertices.
+ * BANDS.  The hull of a union is the hull of the hulls.  hulls.py cuts a job into pieces of at most max_job_pixels pixels and at most
+ * 4095 rows; the host adds the areas, takes the hull (the same monotone chain) of the pieces' ring vertices and recomputes the other
+ * columns from the merged ring by the function hulls_host uses.  No job falls back to the host.
+ * kg_label_hulls: labels = device int32 [nimg][H][W]; jobs = device int32 [m][8] rows {img, id, y1, x1, y2, x2, vert_at, cap}, written
+ * by the caller -> rows = device int64 [m][10], every element written; verts = device int32 [V][2] rows (y, x): ring vertex k of a job
+ * goes to verts[vert_at + k] only inside the unsigned predicates k < cap (a negative cap is 0) and (vert_at + k) < V in 64 bits: a
+ * negative or oversized offset from a wrong table never leaves the buffer.  With slabs of 2 * (h + 1) vertices (one L and one R per
+ * lattice line of the clamped box) no slab can overflow.  Nothing else of verts is touched.
+ * INDEX RULE.  The job table is the one device-read table: box clamped before any address is formed, image index only inside
+ * (unsigned)img < (unsigned)nimg; label values are compared only.  The one new exception is of the run-slot kind: the vertex slot is
+ * vert_at plus a PREFIX COUNT OF PREDICATES, stored only inside the two predicates above.  No atomics on global memory (LDS integer
+ * min / max from run heads and tails only).
+ * One launch whatever m is (one workgroup of 256 per job, the grid strides beyond 2^20 jobs); m == 0 launches nothing (jobs and rows may
+ * then be NULL); V == 0 is valid (verts may then be NULL) and gives the rows alone.  Validates on the host before any HIP call (null
+ * pointers, nimg, H, W > 0, the size rules, m, V >= 0, alignment -- 4 bytes, 8 for the int64 rows --, rows and verts not overlapping
+ * labels, jobs or each other) and never synchronises. */
+int kg_label_hulls(const int* labels, int nimg, int H, int W, const int* jobs, int m, long long* rows, int* verts, int V, void* stream);
 
 /* ---- per-box segmentation branch (KGnet.py:246-267, 321-350): ragged row bookkeeping ---- */
 int kg_seg_build_rows(const int* boxtab8, int nb, int* rowdesc, int* row2box, int* srcrow, void* stream);

@@ -121,6 +121,7 @@ _SIGS = {
     "kg_label_contour_counts": [P, c_int, c_int, c_int, P, c_int, P, P],
     "kg_label_contours": [P, c_int, c_int, c_int, P, c_int, P, c_int, P, c_int, P],
     "kg_polygons_fill": [P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, P, P, P],
+    "kg_label_hulls": [P, c_int, c_int, c_int, P, c_int, P, P, c_int, P],
     "kg_f64_probe": [P, P, P, c_int, P],
     "kg_seg_build_rows": [P, c_int, P, P, P, P],
     "kg_seg_build_rows_levels": [c_int, P, P, P, P, P, P],

@@ -51,6 +51,7 @@ SOURCES = {
     "runlengths.hip": [],
     "contours.hip": [],
     "polygons.hip": [],
+    "hulls.hip": [],
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function"]

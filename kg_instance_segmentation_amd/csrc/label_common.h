@@ -14,7 +14,8 @@
 //   - the run slot of kg_label_runs (runlengths.hip): an offset of the job table plus a prefix count of predicates -- not a label value --
 //     and the store happens only inside the 64-bit unsigned predicate slot < R.  (kg_runs_paint reads a row only at a binary-search
 //     position in [0, R).)  kg_label_contours (contours.hip) stores the same way: ring slot and vertex offset are offsets of the job
-//     table plus prefix counts, inside slot < R and first + k < V;
+//     table plus prefix counts, inside slot < R and first + k < V; and so does kg_label_hulls (hulls.hip): the vertex slot is vert_at of
+//     the job table plus a prefix count, inside k < cap and vert_at + k < V;
 //   - the tracer of contours.hip: its position is an LDS bit index that depends on bits derived from labels.  It is bounded by
 //     construction (a crack touches a P pixel of the box) and by an explicit clamp to [0, h] x [0, w] after every step.  No GLOBAL
 //     address depends on a label there either;

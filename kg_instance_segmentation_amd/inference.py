@@ -119,7 +119,7 @@ def instances_from_predictions(preds):
 
 
 def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None, max_workspace_bytes=None, clean=None, measure=None,
-                      expand=None, neighbours=None, runs=None, contours=None):
+                      expand=None, neighbours=None, runs=None, contours=None, hulls=None):
     """predict(packed=True) followed by the instance label map and the per-instance table of every image (instances.py), on the device:
     the label map (4 bytes per pixel) and the table (64 bytes per instance) replace n full-size masks as what crosses to the host.
     clean: None, or a dict of components.clean's policy arguments: every label map is then cleaned on the device (one components pass
@@ -137,7 +137,10 @@ def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None
     two copies back for all images of one output size.  None adds no launch and no import.
     contours: None; True, or a dict (contours.contours_instances takes no keyword arguments yet, so an empty one): every result's
     `contours` holds the polygon rings of its instances (contours.py: COCO polygons, GeoJSON), taken last, next to runs, on the final
-    label map -- two launches and two copies back for all images of one output size.  None adds no launch and no import."""
+    label map -- two launches and two copies back for all images of one output size.  None adds no launch and no import.
+    hulls: None; True, or a dict of hulls.hulls_instances' keyword arguments (max_job_pixels): every result's `hulls` holds the convex
+    hull of its instances (hulls.py: solidity, Feret diameters, hull rings), taken last, next to contours, on the final label map -- one
+    launch and one copy back for all images of one output size.  None adds no launch and no import."""
     if not torch.is_tensor(x) or x.device.type != "cuda":
         raise _lib.KGLibraryError("predict_instances (MI355X build) needs the input batch on a GPU device")
     out = instances_from_predictions(predict(model, x, nms_thresh, seg_thresh, image_sizes, max_workspace_bytes=max_workspace_bytes, packed=True))
@@ -159,6 +162,9 @@ def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None
     if contours is not None and contours is not False:
         from . import contours as _contours
         _contours.contours_instances_batch(out, **({} if contours is True else dict(contours)))
+    if hulls is not None and hulls is not False:
+        from . import hulls as _hulls
+        _hulls.hulls_instances_batch(out, **({} if hulls is True else dict(hulls)))
     return out
 
 

@@ -29,8 +29,9 @@ class Instances:
     """One image's result of inference.predict_instances: labels = device int32 [h, w]; dets = float32 [n, 5], predict's; table = host
     int64 [n, 8] (TABLE_COLUMNS); masks = the BitMasks; measurements = None unless asked for (measure=, measure.py: a Measurements);
     neighbours = None unless asked for (neighbours=, neighbours.py: a Neighbours); runs = None unless asked for (runs=, runlengths.py: a
-    RunLengths); contours = None unless asked for (contours=, contours.py: a Contours)."""
-    __slots__ = ("labels", "dets", "table", "masks", "measurements", "neighbours", "runs", "contours")
+    RunLengths); contours = None unless asked for (contours=, contours.py: a Contours); hulls = None unless asked for (hulls=, hulls.py: a
+    Hulls)."""
+    __slots__ = ("labels", "dets", "table", "masks", "measurements", "neighbours", "runs", "contours", "hulls")
 
     def __init__(self, labels, dets, table, masks):
         self.labels, self.dets, self.table, self.masks = labels, dets, table, masks
@@ -38,6 +39,7 @@ class Instances:
         self.neighbours = None
         self.runs = None
         self.contours = None
+        self.hulls = None
 
     def __len__(self):
         return len(self.dets)

@@ -217,8 +217,8 @@ class TiledInstances(Instances):
     """predict_tiled's result: labels = device int32 [H, W] (assemble_host: a NumPy array); dets = float32 [n, 5] (y1, x1, y2, x2, conf) in
     global pixels, clipped to the image, in id order; table = host int64 [n, 8]; masks = None; tile int32 [n]; origin int32 [n, 2];
     tile_masks = the tile-local mask rows in id order (BitMasks; assemble_host: uint8 [n, th, tw]): tile_masks[i] placed at origin[i]
-    is the full mask of instance i + 1.  measurements, neighbours, runs and contours are Instances': None unless asked for (measure=,
-    neighbours=, runs=, contours= of predict_tiled)."""
+    is the full mask of instance i + 1.  measurements, neighbours, runs, contours and hulls are Instances': None unless asked for
+    (measure=, neighbours=, runs=, contours=, hulls= of predict_tiled)."""
     __slots__ = ("tile", "origin", "tile_masks")
 
     def __init__(self, labels, dets, table, tile, origin, tile_masks):
@@ -479,7 +479,7 @@ def assemble(plan, per_tile_preds, nms_thresh=0.5, device=None, stage=None, clea
 
 
 def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thresh=0.5, seg_thresh=0.5, max_workspace_bytes=None, stage=None,
-                  clean=None, measure=False, expand=None, neighbours=None, runs=None, contours=None):
+                  clean=None, measure=False, expand=None, neighbours=None, runs=None, contours=None, hulls=None):
     """Instance segmentation of a whole image at native resolution -> TiledInstances.  image: host uint8 [H, W, 3] (uploaded once, to the
     model's device) or a device uint8 tensor; tile: the network input size, (th, tw) or one int, multiples of 32; overlap: pixels two
     neighbouring tiles share at least (choose it at least as large as the largest object: an object is cut at the edge of the tile that
@@ -496,7 +496,10 @@ def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thres
     and two more copies back.  None adds no launch and no import;
     contours: None; True, or a dict (contours.contours_instances takes no keyword arguments yet, so an empty one): the result's
     `contours` then holds the polygon rings of the instances (contours.py: COCO polygons, GeoJSON), taken last, next to runs, on the
-    final label map -- two more launches and two more copies back.  None adds no launch and no import."""
+    final label map -- two more launches and two more copies back.  None adds no launch and no import;
+    hulls: None; True, or a dict of hulls.hulls_instances' keyword arguments (max_job_pixels): the result's `hulls` then holds the convex
+    hull of the instances (hulls.py: solidity, Feret diameters, hull rings), taken last, next to contours, on the final label map -- one
+    more launch and one more copy back.  None adds no launch and no import."""
     import torch
     from . import inference
     if int(batch) < 1:
@@ -534,4 +537,7 @@ def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thres
     if contours is not None and contours is not False:
         from . import contours as _contours
         out.contours = _contours.contours_instances(out, **({} if contours is True else dict(contours)))
+    if hulls is not None and hulls is not False:
+        from . import hulls as _hulls
+        out.hulls = _hulls.hulls_instances(out, **({} if hulls is True else dict(hulls)))
     return out
