@@ -711,6 +711,42 @@ int kg_polygons_fill(const int* edges, int E, const int* items, int n_items, con
  * pointers, nimg, H, W > 0, the size rules, m, V >= 0, alignment -- 4 bytes, 8 for the int64 rows --, rows and verts not overlapping
  * labels, jobs or each other) and never synchronises. */
 int kg_label_hulls(const int* labels, int nimg, int H, int W, const int* jobs, int m, long long* rows, int* verts, int V, void* stream);
+/* Per-instance intensity quantiles and histograms (csrc/intensity.hip; intensity.py states the semantics in NumPy as quantiles_host /
+ * histograms_host): the order statistics the sums of kg_label_measure cannot give -- median, quartiles, a 5 % / 95 % range, a per-object
+ * histogram -- exact in integers.
+ * JOB.  {img, id, y1, x1, y2, x2}, the layout and clamp of kg_label_measure.  P = the pixels of the clamped box in image img with
+ * labels == id.  Labels are compared only: 0, -1, INT_MIN and INT_MAX are ordinary ids.  image = device [nimg][H][W][channels] of unsigned
+ * elements of elem_bytes bytes (1 or 2), 1 <= channels <= 4.  H, W <= 32768 and nimg * H * W <= 2^31 - 1, so a count fits int32.
+ * QUANTILE.  A rational num / den with 0 <= num <= den <= 1 000 000; 1 <= Q <= 8 of them per call, passed as the device table
+ * qtab = int32 [Q][2] rows {num, den}.  For a channel let n = |P| and v_0 <= ... <= v_(n-1) the sorted values of P.  t = num * (n - 1) in
+ * 64 bits; k_lo = t / den, rem = t % den, k_hi = k_lo + (rem != 0).  The device returns the two order statistics lo = v_(k_lo) and
+ * hi = v_(k_hi).
+ * ROW.  out = device int32 [m][channels][1 + 2 Q] = {n, lo_0, hi_0, ..., lo_(Q-1), hi_(Q-1)}, every element written.  A bad job -- an image
+ * index outside [0, nimg), an empty or inverted box, an id the box does not hold -- gets zeros everywhere.  A table row with den <= 0,
+ * num < 0 or num > den yields lo = hi = 0 for that quantile without a division.
+ * HOST-DERIVED VALUES.  From those integers only, in float64, in code the device route and the host statement share (intensity.py,
+ * Quantiles): lower = lo; higher = hi; linear = lo + (hi - lo) * rem / den, numpy's default percentile; iqr where both 1/4 and 3/4 were
+ * asked for; n == 0 gives NaN.
+ * HISTOGRAM.  A histogram job is int32 [9] = {img, id, y1, x1, y2, x2, channel, shift, prefix}; out = device int32 [m][256], every element
+ * written.  With w = value >> shift, 0 <= shift <= 8: prefix < 0: every pixel of P counts into bin min(w, 255), so bin 255 is "255 and
+ * above"; prefix >= 0: only the pixels with (w >> 8) == prefix count, into bin w & 255.  channel is used only inside
+ * (unsigned)channel < (unsigned)channels and shift only inside (unsigned)shift <= 8: a job that fails either, or is a bad job as above,
+ * gets a row of zeros.  8-bit data with shift = 0, prefix = -1 is the exact 256-bin histogram; 16-bit data with shift = 4 the exact
+ * histogram of 12-bit camera data; shift = 8 the histogram of the high byte, and shift = 0, prefix = b that of the low bytes under high
+ * byte b: the two levels intensity.py selects a quantile of a job too large for one workgroup from.
+ * INDEX RULE.  The one new exception of the family: an LDS bin index formed from a pixel value, bounded by construction (& 255, after
+ * min(., 255) where the last bin collects, immediately before use, inside a 256-entry array).  No GLOBAL address depends on a pixel or
+ * label value; the job table's box is clamped before any address is formed, its image index is used only inside
+ * (unsigned)img < (unsigned)nimg; qtab is read at fixed positions.  A wrong job or quantile table gives wrong numbers and cannot leave
+ * the buffers.  LDS integer atomics only, none on global memory: the counts are integers, so no order of execution changes a result.
+ * One launch each whatever m is (one workgroup of 256 per job, the grid strides beyond 2^20 jobs and clears its LDS per job); m == 0
+ * launches nothing (jobs and out may then be NULL).  Both validate on the host before any HIP call (null pointers -- image included --,
+ * nimg, H, W > 0, the size rules, channels in 1 .. 4, elem_bytes in {1, 2}, Q in 1 .. 8, m >= 0, 4-byte alignment of labels, jobs, qtab
+ * and out, 2 of a 2-byte image) and never synchronise. */
+int kg_label_quantiles(const int* labels, int nimg, int H, int W, const void* image, int channels, int elem_bytes, const int* jobs, int m,
+                       const int* qtab, int Q, int* out, void* stream);
+int kg_label_histograms(const int* labels, int nimg, int H, int W, const void* image, int channels, int elem_bytes, const int* jobs, int m,
+                        int* out, void* stream);
 
 /* ---- per-box segmentation branch (KGnet.py:246-267, 321-350): ragged row bookkeeping ---- */
 int kg_seg_build_rows(const int* boxtab8, int nb, int* rowdesc, int* row2box, int* srcrow, void* stream);

@@ -52,6 +52,7 @@ SOURCES = {
     "contours.hip": [],
     "polygons.hip": [],
     "hulls.hip": [],
+    "intensity.hip": [],
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function"]

@@ -1,11 +1,11 @@
-// label_common.h -- what the label-map kernels share (instances.hip, tiling.hip, labelmetrics.hip, components.hip, measure.hip; paste.hip for
+// label_common.h -- what the label-map kernels share (instances.hip, tiling.hip, labelmetrics.hip, components.hip, measure.hip, intensity.hip; paste.hip for
 // the bit-mask leading dimension): wave reductions, the clamped job box and its walk, the block combine of four wave partials, the
 // row-segment run walk, per-image ranges passed by value, and the host argument checks.  Integers only, plain C++ and vector memory
 // operations only.
 //
 // INDEX RULE of the family.  Every entry validates on the host before any HIP call and never synchronises; the number of launches does
 // not depend on a count read from the device; every output element is written.  No address in a kernel depends on a value read from
-// device memory, with five kinds of exception, each bounded where it is made:
+// device memory, with six kinds of exception, each bounded where it is made:
 //   - a job table (a device table the caller wrote): its box is clamped to the map BEFORE any address is formed (kg_job_box), and any
 //     other index it carries is used only inside an unsigned range predicate that empties the box when it fails, so even a wrong table
 //     cannot make a kernel leave its buffers;
@@ -23,6 +23,10 @@
 //     range clamped inside [0, n_items] (a decreasing pair is an empty range), and an item's edge_first, edge_count only inside the 64-bit
 //     unsigned predicates first <= E and count <= E - first, which empty the item when they fail.  No address depends on an edge
 //     coordinate, a value or a row: a wrong table gives wrong pixels and cannot reach outside edges, items, out or cover.
+//   - the LDS histogram of intensity.hip (kg_label_quantiles, kg_label_histograms): an LDS bin index formed from a PIXEL VALUE, the first
+//     of the family.  It is bounded by construction: `& 255` (after min(., 255) where the last bin collects) immediately before use, inside
+//     int [256]; the low-byte histogram a rank selected is an LDS row index used only inside (unsigned)s < (unsigned)KEEP.  No GLOBAL
+//     address depends on a pixel or label value there either.
 // Labels and pixel values are otherwise predicates, summands and stored values only.
 #pragma once
 #include "kg_common.h"

@@ -119,7 +119,7 @@ def instances_from_predictions(preds):
 
 
 def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None, max_workspace_bytes=None, clean=None, measure=None,
-                      expand=None, neighbours=None, runs=None, contours=None, hulls=None):
+                      expand=None, neighbours=None, runs=None, contours=None, hulls=None, quantiles=None):
     """predict(packed=True) followed by the instance label map and the per-instance table of every image (instances.py), on the device:
     the label map (4 bytes per pixel) and the table (64 bytes per instance) replace n full-size masks as what crosses to the host.
     clean: None, or a dict of components.clean's policy arguments: every label map is then cleaned on the device (one components pass
@@ -140,7 +140,11 @@ def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None
     label map -- two launches and two copies back for all images of one output size.  None adds no launch and no import.
     hulls: None; True, or a dict of hulls.hulls_instances' keyword arguments (max_job_pixels): every result's `hulls` holds the convex
     hull of its instances (hulls.py: solidity, Feret diameters, hull rings), taken last, next to contours, on the final label map -- one
-    launch and one copy back for all images of one output size.  None adds no launch and no import."""
+    launch and one copy back for all images of one output size.  None adds no launch and no import.
+    quantiles: None; a uint8 / uint16 [N, h, w, C] array or device tensor at the label maps' size, or a dict {"image": that, "q": ...,
+    "max_job_pixels": ...} of intensity.quantiles_instances_batch's arguments: every result's `quantiles` holds the intensity order
+    statistics of its instances (intensity.py: median, quartiles, a 5 % / 95 % range), taken next to measure on the final label map -- one
+    launch, one upload and one copy back for all images of one output size.  None adds no launch and no import."""
     if not torch.is_tensor(x) or x.device.type != "cuda":
         raise _lib.KGLibraryError("predict_instances (MI355X build) needs the input batch on a GPU device")
     out = instances_from_predictions(predict(model, x, nms_thresh, seg_thresh, image_sizes, max_workspace_bytes=max_workspace_bytes, packed=True))
@@ -153,6 +157,10 @@ def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None
     if measure is not None and measure is not False:
         from . import measure as _measure
         _measure.measure_instances_batch(out, None if measure is True else measure)
+    if quantiles is not None and quantiles is not False:
+        from . import intensity
+        kw = dict(quantiles) if isinstance(quantiles, dict) else {"image": quantiles}
+        intensity.quantiles_instances_batch(out, kw.pop("image", None), **kw)
     if neighbours is not None and neighbours is not False:
         from . import neighbours as _neighbours
         _neighbours.neighbours_instances_batch(out, **({} if neighbours is True else dict(neighbours)))

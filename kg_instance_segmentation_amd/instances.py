@@ -30,8 +30,8 @@ class Instances:
     int64 [n, 8] (TABLE_COLUMNS); masks = the BitMasks; measurements = None unless asked for (measure=, measure.py: a Measurements);
     neighbours = None unless asked for (neighbours=, neighbours.py: a Neighbours); runs = None unless asked for (runs=, runlengths.py: a
     RunLengths); contours = None unless asked for (contours=, contours.py: a Contours); hulls = None unless asked for (hulls=, hulls.py: a
-    Hulls)."""
-    __slots__ = ("labels", "dets", "table", "masks", "measurements", "neighbours", "runs", "contours", "hulls")
+    Hulls); quantiles = None unless asked for (quantiles=, intensity.py: a Quantiles)."""
+    __slots__ = ("labels", "dets", "table", "masks", "measurements", "neighbours", "runs", "contours", "hulls", "quantiles")
 
     def __init__(self, labels, dets, table, masks):
         self.labels, self.dets, self.table, self.masks = labels, dets, table, masks
@@ -40,6 +40,7 @@ class Instances:
         self.runs = None
         self.contours = None
         self.hulls = None
+        self.quantiles = None
 
     def __len__(self):
         return len(self.dets)

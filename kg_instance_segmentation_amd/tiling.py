@@ -217,8 +217,8 @@ class TiledInstances(Instances):
     """predict_tiled's result: labels = device int32 [H, W] (assemble_host: a NumPy array); dets = float32 [n, 5] (y1, x1, y2, x2, conf) in
     global pixels, clipped to the image, in id order; table = host int64 [n, 8]; masks = None; tile int32 [n]; origin int32 [n, 2];
     tile_masks = the tile-local mask rows in id order (BitMasks; assemble_host: uint8 [n, th, tw]): tile_masks[i] placed at origin[i]
-    is the full mask of instance i + 1.  measurements, neighbours, runs, contours and hulls are Instances': None unless asked for
-    (measure=, neighbours=, runs=, contours=, hulls= of predict_tiled)."""
+    is the full mask of instance i + 1.  measurements, neighbours, runs, contours, hulls and quantiles are Instances': None unless asked for
+    (measure=, neighbours=, runs=, contours=, hulls=, quantiles= of predict_tiled)."""
     __slots__ = ("tile", "origin", "tile_masks")
 
     def __init__(self, labels, dets, table, tile, origin, tile_masks):
@@ -479,7 +479,7 @@ def assemble(plan, per_tile_preds, nms_thresh=0.5, device=None, stage=None, clea
 
 
 def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thresh=0.5, seg_thresh=0.5, max_workspace_bytes=None, stage=None,
-                  clean=None, measure=False, expand=None, neighbours=None, runs=None, contours=None, hulls=None):
+                  clean=None, measure=False, expand=None, neighbours=None, runs=None, contours=None, hulls=None, quantiles=None):
     """Instance segmentation of a whole image at native resolution -> TiledInstances.  image: host uint8 [H, W, 3] (uploaded once, to the
     model's device) or a device uint8 tensor; tile: the network input size, (th, tw) or one int, multiples of 32; overlap: pixels two
     neighbouring tiles share at least (choose it at least as large as the largest object: an object is cut at the edge of the tile that
@@ -499,9 +499,14 @@ def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thres
     final label map -- two more launches and two more copies back.  None adds no launch and no import;
     hulls: None; True, or a dict of hulls.hulls_instances' keyword arguments (max_job_pixels): the result's `hulls` then holds the convex
     hull of the instances (hulls.py: solidity, Feret diameters, hull rings), taken last, next to contours, on the final label map -- one
-    more launch and one more copy back.  None adds no launch and no import."""
+    more launch and one more copy back.  None adds no launch and no import;
+    quantiles: None; True, or a dict of intensity.quantiles_instances' keyword arguments (q, max_job_pixels): the result's `quantiles`
+    then holds the intensity order statistics of the instances (intensity.py: median, quartiles, a 5 % / 95 % range) against the uploaded
+    uint8 image, taken next to measure on the final label map -- one more launch, upload and copy back.  None adds no launch and no
+    import."""
     import torch
     from . import inference
+    quantiles = None if quantiles is False else quantiles
     if int(batch) < 1:
         raise KGLibraryError(f"predict_tiled: batch {batch}")
     mark = stage if stage is not None else (lambda name: None)
@@ -509,7 +514,7 @@ def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thres
         shape, dev = tuple(image.shape), image.device
     else:
         shape, dev = _host_image(image).shape, next(model.parameters()).device
-        if measure:                                                   # the one upload serves the tiles and the measurements
+        if measure or quantiles is not None:                          # the one upload serves the tiles and the measurements
             from . import ops
             image = ops.h2d(_host_image(image), dev)
     if len(shape) != 3 or shape[2] != 3:
@@ -528,6 +533,9 @@ def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thres
     if measure:
         from . import measure as _measure
         out.measurements = _measure.measure_instances(out, image)
+    if quantiles is not None:
+        from . import intensity
+        out.quantiles = intensity.quantiles_instances(out, image, **({} if quantiles is True else dict(quantiles)))
     if neighbours is not None and neighbours is not False:
         from . import neighbours as _neighbours
         out.neighbours = _neighbours.neighbours_instances(out, **({} if neighbours is True else dict(neighbours)))
