@@ -747,6 +747,53 @@ int kg_label_quantiles(const int* labels, int nimg, int H, int W, const void* im
                        const int* qtab, int Q, int* out, void* stream);
 int kg_label_histograms(const int* labels, int nimg, int H, int W, const void* image, int channels, int elem_bytes, const int* jobs, int m,
                         int* out, void* stream);
+/* Merged instances split (csrc/split.hip; split.py states the semantics in NumPy as split_host / regrow_host): two touching nuclei
+ * under one id become two ids again -- core seeds, then a seeded geodesic regrow inside the instance.  Everything is an exact integer.
+ * SPLIT, the statement split.py composes from existing entries plus kg_label_split.  Inputs: a label map with ids 1 .. n per image, a
+ * distance 1 <= d <= 64, connectivity c in {4, 8}, min_seed_area >= 1, frame, and `only` (all ids, or the ids that may be split).
+ *   1. CORE.  core = the shrunk labels of kg_label_regrow (op 2) at distance d with the same frame.
+ *   2. SEEDS.  The components of core under kg_label_components with connectivity c and bg_connectivity 0.  A seed of id k is a
+ *      component of value k with area >= min_seed_area; the seeds of k get ranks 1 .. S_k in ascending component number, which is the
+ *      raster order of their first pixels.
+ *   3. WHICH.  An id with S_k <= 1, or not in `only`, is untouched.
+ *   4. REGROW, for an id with S_k >= 2, over P = the pixels of the id's box with labels == k: see REGROW below.
+ *   5. IDS.  Rank 1 keeps k; rank r >= 2 becomes first_new_k + r - 2; the new ids are n + 1, n + 2, ... per image in ascending (k, r).
+ *      Every other pixel is copied.
+ *   6. RESULTS.  parent = int32 [n_new]: row i < n is i itself, the row of a new id is k - 1.  The per-instance table comes from
+ *      kg_label_table over the parents' boxes; a new row's area_full is its parent's.
+ * JOB.  {img, id, y1, x1, y2, x2, nseeds, first_new}, a half-open box clamped to the map.  P = the pixels of the clamped box in image img
+ * with labels == id.  Values are compared only: 0, -1, INT_MIN and INT_MAX are ordinary ids.  H, W <= 32768 as for kg_label_measure.
+ * SEED MAP.  seeds = device int32 of the labels' shape, ANY values.  The rank of a pixel p of P is seeds[p] when
+ * 1 <= seeds[p] <= min(nseeds, 16382), else 0 (no seed); a seeds value on a pixel outside P is never used.  Seed s is the set of the
+ * pixels of P with rank s; it need not be connected, and a rank may be empty.
+ * REGROW.  Two pixels are adjacent when they differ by one step along an axis (c = 4) or also along a diagonal (c = 8).  g(p, s) is the
+ * number of steps of the shortest path of adjacent pixels from p to any pixel of seed s that stays inside P: 0 on the seed, infinite
+ * without such a path.  A pixel p of P goes to the seed of smallest rank among those with the smallest finite g(p, s).  A pixel no seed
+ * reaches is UNREACHED and is handled as rank 1: a piece of the id that holds no seed stays with the id.  Equivalently, a
+ * level-synchronous flood: level 0 assigns the seeds; in level L + 1 every unassigned pixel of P with a neighbour assigned in levels <= L
+ * takes the smallest rank among those neighbours.  (By induction a pixel is assigned in level min_s g(p, s), and the ranks its
+ * neighbours of the level before carry are exactly the ranks s with g(p, s) minimal.)  The result does not depend on any scheduling order.
+ * OUTPUT.  out = device int32 of the labels' shape, not overlapping labels or seeds.  The entry fills it as a copy of labels on the stream;
+ * the kernel then stores first_new + r - 2 (32-bit wrap-around) on the pixels of rank r >= 2 and nothing else, so every element is
+ * written.  Two jobs of one image with different ids never store the same pixel; two jobs with the same id and overlapping boxes are
+ * the caller's error (the pixel then holds the value of either).
+ * ROW.  rows = device int32 [m][4] = {members, unreached, levels, status}, every element written: members = |P|, unreached as above,
+ * levels = the largest finite min_s g(p, s) over P (0 without a seed).  A bad job -- an image index outside [0, nimg), an empty or inverted
+ * box, an id the box does not hold -- gets zeros and stores nothing.
+ * SIZE.  A job is regrown on the device when its state fits 32 KiB of LDS at 16 bits per pixel with a one-pixel zero halo: with h, w the
+ * clamped box, (h + 2) * (w + 2) <= 16384 (126 x 126, or 1 x 5459).  A job that does not fit gets the row {0, 0, 0, 1} and is left as
+ * copied.  A geodesic flood cannot be banded, so split.py regrows such a box on the host from that box copied back and writes it in.
+ * kg_label_split: labels, seeds = device int32 [nimg][H][W]; connectivity = 4 or 8; jobs = device int32 [m][8], written by the caller.
+ * INDEX RULE.  No new exception.  The job table is the one device-read table: box clamped before any address is formed, image index only
+ * inside (unsigned)img < (unsigned)nimg; nseeds is the bound of a predicate and first_new a stored value, never an address.  The LDS state
+ * is indexed by box-local coordinates alone: no LDS or global address depends on a label, a seed or a rank.  No atomics, no global
+ * scratch.
+ * One copy and ONE launch whatever m is (one workgroup of 256 per job, the grid strides beyond 2^20 jobs); m == 0 launches only the copy
+ * (jobs and rows may then be NULL).  Validates on the host before any HIP call (null pointers, nimg, H, W > 0, the size rules, the
+ * connectivity, m >= 0, 4-byte alignment, out not overlapping labels or seeds, rows not overlapping a map, jobs not overlapping out or
+ * rows) and never synchronises. */
+int kg_label_split(const int* labels, const int* seeds, int nimg, int H, int W, int connectivity, const int* jobs, int m, int* out, int* rows,
+                   void* stream);
 
 /* ---- per-box segmentation branch (KGnet.py:246-267, 321-350): ragged row bookkeeping ---- */
 int kg_seg_build_rows(const int* boxtab8, int nb, int* rowdesc, int* row2box, int* srcrow, void* stream);

@@ -53,6 +53,7 @@ SOURCES = {
     "polygons.hip": [],
     "hulls.hip": [],
     "intensity.hip": [],
+    "split.hip": [],
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function"]

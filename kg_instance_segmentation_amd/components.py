@@ -355,11 +355,14 @@ def clean(labels, n, keep="largest", min_area=0, fill_holes=True, max_hole_area=
 
 
 def _like(inst, labels, table):
-    """A new object of inst's type with labels and table replaced; everything else is kept."""
+    """A new object of inst's type with labels and table replaced; dets, the masks and parent (split.py) are kept."""
     from .tiling import TiledInstances
     if isinstance(inst, TiledInstances):
-        return TiledInstances(labels, inst.dets, table, inst.tile, inst.origin, inst.tile_masks)
-    return Instances(labels, inst.dets, table, inst.masks)
+        new = TiledInstances(labels, inst.dets, table, inst.tile, inst.origin, inst.tile_masks)
+    else:
+        new = Instances(labels, inst.dets, table, inst.masks)
+    new.parent = inst.parent
+    return new
 
 
 def _instance_policy(fn, policy):

@@ -1,4 +1,4 @@
-// label_common.h -- what the label-map kernels share (instances.hip, tiling.hip, labelmetrics.hip, components.hip, measure.hip, intensity.hip; paste.hip for
+// label_common.h -- what the label-map kernels share (instances.hip, tiling.hip, labelmetrics.hip, components.hip, measure.hip, intensity.hip, split.hip; paste.hip for
 // the bit-mask leading dimension): wave reductions, the clamped job box and its walk, the block combine of four wave partials, the
 // row-segment run walk, per-image ranges passed by value, and the host argument checks.  Integers only, plain C++ and vector memory
 // operations only.
@@ -27,7 +27,9 @@
 //     of the family.  It is bounded by construction: `& 255` (after min(., 255) where the last bin collects) immediately before use, inside
 //     int [256]; the low-byte histogram a rank selected is an LDS row index used only inside (unsigned)s < (unsigned)KEEP.  No GLOBAL
 //     address depends on a pixel or label value there either.
-// Labels and pixel values are otherwise predicates, summands and stored values only.
+// Labels and pixel values are otherwise predicates, summands and stored values only.  kg_label_split (split.hip) adds NO exception: its
+// LDS state is indexed by box-local coordinates alone, never by a label, a seed or a rank, and nseeds / first_new of its job table are a
+// predicate bound and a stored value.
 #pragma once
 #include "kg_common.h"
 #include <limits.h>

@@ -119,7 +119,7 @@ def instances_from_predictions(preds):
 
 
 def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None, max_workspace_bytes=None, clean=None, measure=None,
-                      expand=None, neighbours=None, runs=None, contours=None, hulls=None, quantiles=None):
+                      expand=None, neighbours=None, runs=None, contours=None, hulls=None, quantiles=None, split=None):
     """predict(packed=True) followed by the instance label map and the per-instance table of every image (instances.py), on the device:
     the label map (4 bytes per pixel) and the table (64 bytes per instance) replace n full-size masks as what crosses to the host.
     clean: None, or a dict of components.clean's policy arguments: every label map is then cleaned on the device (one components pass
@@ -144,13 +144,21 @@ def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None
     quantiles: None; a uint8 / uint16 [N, h, w, C] array or device tensor at the label maps' size, or a dict {"image": that, "q": ...,
     "max_job_pixels": ...} of intensity.quantiles_instances_batch's arguments: every result's `quantiles` holds the intensity order
     statistics of its instances (intensity.py: median, quartiles, a 5 % / 95 % range), taken next to measure on the final label map -- one
-    launch, one upload and one copy back for all images of one output size.  None adds no launch and no import."""
+    launch, one upload and one copy back for all images of one output size.  None adds no launch and no import.
+    split: None; a distance in pixels (a number, 1 .. 64), or a dict of split.split_instances_batch's arguments (distance, connectivity,
+    min_seed_area, frame, only): merged instances are then split into their core seeds' regions (split.py), after the clean-up and
+    before the expansion and everything else; every result has `parent` set, dets extended by a copy of the parent's row per new id and
+    masks unchanged.  One seeds pass and one kg_label_split launch for all images of one output size.  None adds no launch and no
+    import."""
     if not torch.is_tensor(x) or x.device.type != "cuda":
         raise _lib.KGLibraryError("predict_instances (MI355X build) needs the input batch on a GPU device")
     out = instances_from_predictions(predict(model, x, nms_thresh, seg_thresh, image_sizes, max_workspace_bytes=max_workspace_bytes, packed=True))
     if clean is not None:
         from . import components
         out = components.clean_instances_batch(out, **dict(clean))
+    if split is not None:
+        from . import split as _split
+        out = _split.split_instances_batch(out, **(dict(split) if isinstance(split, dict) else {"distance": split}))
     if expand is not None:
         from . import distance
         out = distance.expand_instances_batch(out, expand)

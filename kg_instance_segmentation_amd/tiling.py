@@ -218,7 +218,9 @@ class TiledInstances(Instances):
     global pixels, clipped to the image, in id order; table = host int64 [n, 8]; masks = None; tile int32 [n]; origin int32 [n, 2];
     tile_masks = the tile-local mask rows in id order (BitMasks; assemble_host: uint8 [n, th, tw]): tile_masks[i] placed at origin[i]
     is the full mask of instance i + 1.  measurements, neighbours, runs, contours, hulls and quantiles are Instances': None unless asked for
-    (measure=, neighbours=, runs=, contours=, hulls=, quantiles= of predict_tiled)."""
+    (measure=, neighbours=, runs=, contours=, hulls=, quantiles= of predict_tiled).  parent is Instances' too: None unless a split ran
+    (split=, split.py); then dets, tile and origin hold a copy of the parent's row for every new id and tile_masks keeps the rows of the
+    parents only: tile_masks[parent[i]] placed at origin[i] is the mask instance i + 1 came from."""
     __slots__ = ("tile", "origin", "tile_masks")
 
     def __init__(self, labels, dets, table, tile, origin, tile_masks):
@@ -412,7 +414,7 @@ def table_from_labels(labels, jobs, area_full=None):
     return table
 
 
-def assemble(plan, per_tile_preds, nms_thresh=0.5, device=None, stage=None, clean=None):
+def assemble(plan, per_tile_preds, nms_thresh=0.5, device=None, stage=None, clean=None, split=None):
     """Everything after the per-tile predict calls.  per_tile_preds: per tile None or predict(packed=True)'s [BitMasks of th x tw, dets];
     the masks of a tile that reaches past the image are clipped in place.  device: where an empty result's labels go when no tile has a
     detection (default: the masks' device, else the current GPU).  stage: optional callable(name), called on the stream before the label
@@ -420,7 +422,13 @@ def assemble(plan, per_tile_preds, nms_thresh=0.5, device=None, stage=None, clea
     Host <-> device traffic: ONE upload (the job table, with the ids and the row indices of the two mask gathers behind it) and ONE
     device -> host copy (the global table).
     clean: None, or a dict of components.clean's policy arguments: the stitched map then goes through components.clean_instances (its
-    launches and copies on top)."""
+    launches and copies on top).
+    split: None, a distance in pixels, or a dict of split.split_instances' arguments: the (cleaned) stitched map then goes through
+    split.split_instances (its launches and copies on top); None adds no launch and no import."""
+    if split is not None:
+        from . import split as _split
+        return _split.split_instances(assemble(plan, per_tile_preds, nms_thresh, device, stage, clean),
+                                      **(dict(split) if isinstance(split, dict) else {"distance": split}))
     if clean is not None:
         from . import components
         return components.clean_instances(assemble(plan, per_tile_preds, nms_thresh, device, stage), **dict(clean))
@@ -479,7 +487,7 @@ def assemble(plan, per_tile_preds, nms_thresh=0.5, device=None, stage=None, clea
 
 
 def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thresh=0.5, seg_thresh=0.5, max_workspace_bytes=None, stage=None,
-                  clean=None, measure=False, expand=None, neighbours=None, runs=None, contours=None, hulls=None, quantiles=None):
+                  clean=None, measure=False, expand=None, neighbours=None, runs=None, contours=None, hulls=None, quantiles=None, split=None):
     """Instance segmentation of a whole image at native resolution -> TiledInstances.  image: host uint8 [H, W, 3] (uploaded once, to the
     model's device) or a device uint8 tensor; tile: the network input size, (th, tw) or one int, multiples of 32; overlap: pixels two
     neighbouring tiles share at least (choose it at least as large as the largest object: an object is cut at the edge of the tile that
@@ -503,7 +511,11 @@ def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thres
     quantiles: None; True, or a dict of intensity.quantiles_instances' keyword arguments (q, max_job_pixels): the result's `quantiles`
     then holds the intensity order statistics of the instances (intensity.py: median, quartiles, a 5 % / 95 % range) against the uploaded
     uint8 image, taken next to measure on the final label map -- one more launch, upload and copy back.  None adds no launch and no
-    import."""
+    import;
+    split: None; a distance in pixels (1 .. 64), or a dict of split.split_instances' arguments (distance, connectivity, min_seed_area,
+    frame, only): merged instances of the STITCHED map are then split into their core seeds' regions (split.py, through assemble), after
+    the clean-up and before the expansion and everything else; the result has `parent` set, dets / tile / origin extended by a copy of
+    the parent's row per new id and tile_masks unchanged.  None adds no launch and no import."""
     import torch
     from . import inference
     quantiles = None if quantiles is False else quantiles
@@ -526,7 +538,7 @@ def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thres
     preds = []
     for a in range(0, len(pl), int(batch)):
         preds += inference.predict(model, x[a:a + int(batch)], nms_thresh, seg_thresh, None, max_workspace_bytes=max_workspace_bytes, packed=True)
-    out = assemble(pl, preds, nms_thresh, dev, stage, clean)
+    out = assemble(pl, preds, nms_thresh, dev, stage, clean, split)
     if expand is not None:
         from . import distance
         out = distance.expand_instances(out, expand)
