@@ -794,6 +794,43 @@ int kg_label_histograms(const int* labels, int nimg, int H, int W, const void* i
  * rows) and never synchronises. */
 int kg_label_split(const int* labels, const int* seeds, int nimg, int H, int W, int connectivity, const int* jobs, int m, int* out, int* rows,
                    void* stream);
+/* Per-instance texture (csrc/texture.hip; texture.py states the semantics in NumPy as glcm_host): the grey-level co-occurrence matrices
+ * of every instance, from which the host derives Haralick's features -- what an instance looks like inside.  A co-occurrence count is a
+ * function of PAIRS of pixels: no function of the sums of kg_label_measure or of the bins of kg_label_histograms.  Exact in integers.
+ * JOB.  int32 [10] = {img, id, y1, x1, y2, x2, channel, distance, lo, span}: a half-open box with the clamp of kg_label_measure.  P = the
+ * pixels of the clamped box in image img with labels == id.  Labels are compared only: 0, -1, INT_MIN and INT_MAX are ordinary ids.
+ * image = device [nimg][H][W][channels] of unsigned elements of elem_bytes bytes (1 or 2), 1 <= channels <= 4.  H, W <= 32768 and
+ * nimg * H * W <= 2^31 - 1, the rules of kg_label_quantiles, so a count fits int32.
+ * LEVEL.  For a pixel value v of channel `channel`: u = max(v - lo, 0), lev = min(u * L / span, L - 1), with 2 <= L <= 32 the per-call
+ * argument `levels` and the quotient rounded down.  The value is the exact one for every lo and span > 0 (the int32 one wherever int32
+ * does not overflow).  8-bit data with lo = 0, span = 256, L = 16 gives v >> 4; a 12-bit camera uses span = 4096; per-object normalisation
+ * uses lo = min, span = max - min + 1 from kg_label_measure.
+ * DIRECTIONS.  Four, numbered 0 .. 3, with offsets (dy, dx) = (0, d), (d, d), (d, 0), (d, -d), d = distance.  G[k][i][j] = the number of
+ * pixels p of P such that p + o_k lies inside the H x W map, carries the label id, lev at p is i and lev at p + o_k is j.  The partner is
+ * read from the MAP, never from the box: a box that cuts an object still counts the pairs that leave the box, and so the matrices of
+ * disjoint pieces of a box add up exactly (the banding argument of kg_label_measure).  The matrix of the opposite offset -o_k is the
+ * transpose of G[k] taken over the whole object; G + G^T is the symmetric matrix Haralick's features are defined on.
+ * ROW.  out = device int32 [m][4][L][L], every element written.  A bad job gets zeros, and nothing divides by span unless it is positive:
+ * img outside [0, nimg); an empty or inverted box; channel failing (unsigned)channel < (unsigned)channels; distance failing
+ * (unsigned)(distance - 1) < 32; span <= 0.
+ * ROUTES.  A workgroup whose clamped box has (h + d) * (w + 2 d) <= 16384 stages the rectangle of rows y1 .. y2 - 1 + d and columns
+ * x1 - d .. x2 - 1 + d into LDS, one byte per pixel (the level, or 0xFF for a pixel outside the map or of another label), so that every
+ * pixel is loaded and divided once, and counts the pairs from LDS; a larger box counts them straight from global memory.  The route is
+ * chosen from the clamped box and d alone, uniformly per workgroup, and both give the same rows.
+ * HOST-DERIVED VALUES.  From those integers only, in float64, in code the device route and the host statement share (texture.py,
+ * CoMatrices): pairs, the symmetric matrix, Haralick's f1 .. f13 (the formulas stand in texture.py).
+ * INDEX RULE.  The exception of kg_label_quantiles' kind: an LDS index formed from pixel values, i * L + j, each level bounded by
+ * min(., L - 1) immediately before use, inside int [4][1024].  The staged byte is indexed by a box-local coordinate alone.  No GLOBAL
+ * address depends on a pixel or label value; the job table's box is clamped before any address is formed; img, channel, distance and span
+ * are used only inside the predicates above, which empty the box when they fail; lo is subtracted and compared only.  A wrong job table
+ * gives wrong numbers and cannot leave the buffers.  LDS integer atomics only, none on global memory: no order of execution changes a
+ * result; out is written with plain vector stores.
+ * One launch whatever m is (one workgroup of 256 per job, the grid strides beyond 2^20 jobs and clears its LDS per job); m == 0 launches
+ * nothing (jobs and out may then be NULL).  Validates on the host before any HIP call (null pointers -- image included --, nimg, H, W > 0,
+ * the size rules, channels in 1 .. 4, elem_bytes in {1, 2}, levels in 2 .. 32, m >= 0, 4-byte alignment of labels, jobs and out, 2 of a
+ * 2-byte image) and never synchronises. */
+int kg_label_glcm(const int* labels, int nimg, int H, int W, const void* image, int channels, int elem_bytes, const int* jobs, int m,
+                  int levels, int* out, void* stream);
 
 /* ---- per-box segmentation branch (KGnet.py:246-267, 321-350): ragged row bookkeeping ---- */
 int kg_seg_build_rows(const int* boxtab8, int nb, int* rowdesc, int* row2box, int* srcrow, void* stream);

@@ -1,4 +1,4 @@
-"""The argument layer the label-map modules share (instances, tiling, labelmetrics, components, measure, neighbours, runlengths, contours, split): label maps
+"""The argument layer the label-map modules share (instances, tiling, labelmetrics, components, measure, neighbours, runlengths, contours, split, texture): label maps
 and job tables, host or device.  fn is the public function the message names."""
 import numpy as np
 

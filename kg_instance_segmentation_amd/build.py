@@ -54,6 +54,7 @@ SOURCES = {
     "hulls.hip": [],
     "intensity.hip": [],
     "split.hip": [],
+    "texture.hip": [],
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function"]

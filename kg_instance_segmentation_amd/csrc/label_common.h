@@ -1,4 +1,4 @@
-// label_common.h -- what the label-map kernels share (instances.hip, tiling.hip, labelmetrics.hip, components.hip, measure.hip, intensity.hip, split.hip; paste.hip for
+// label_common.h -- what the label-map kernels share (instances.hip, tiling.hip, labelmetrics.hip, components.hip, measure.hip, intensity.hip, split.hip, texture.hip; paste.hip for
 // the bit-mask leading dimension): wave reductions, the clamped job box and its walk, the block combine of four wave partials, the
 // row-segment run walk, per-image ranges passed by value, and the host argument checks.  Integers only, plain C++ and vector memory
 // operations only.
@@ -26,7 +26,9 @@
 //   - the LDS histogram of intensity.hip (kg_label_quantiles, kg_label_histograms): an LDS bin index formed from a PIXEL VALUE, the first
 //     of the family.  It is bounded by construction: `& 255` (after min(., 255) where the last bin collects) immediately before use, inside
 //     int [256]; the low-byte histogram a rank selected is an LDS row index used only inside (unsigned)s < (unsigned)KEEP.  No GLOBAL
-//     address depends on a pixel or label value there either.
+//     address depends on a pixel or label value there either.  The co-occurrence matrices of texture.hip (kg_label_glcm) are of the same
+//     kind: the LDS index i * L + j is formed from two pixel LEVELS, each bounded by min(., L - 1) immediately before use, inside
+//     int [4][1024] with L <= 32; its staged bytes are indexed by box-local coordinates alone.
 // Labels and pixel values are otherwise predicates, summands and stored values only.  kg_label_split (split.hip) adds NO exception: its
 // LDS state is indexed by box-local coordinates alone, never by a label, a seed or a rank, and nseeds / first_new of its job table are a
 // predicate bound and a stored value.

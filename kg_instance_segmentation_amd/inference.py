@@ -119,7 +119,7 @@ def instances_from_predictions(preds):
 
 
 def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None, max_workspace_bytes=None, clean=None, measure=None,
-                      expand=None, neighbours=None, runs=None, contours=None, hulls=None, quantiles=None, split=None):
+                      expand=None, neighbours=None, runs=None, contours=None, hulls=None, quantiles=None, split=None, texture=None):
     """predict(packed=True) followed by the instance label map and the per-instance table of every image (instances.py), on the device:
     the label map (4 bytes per pixel) and the table (64 bytes per instance) replace n full-size masks as what crosses to the host.
     clean: None, or a dict of components.clean's policy arguments: every label map is then cleaned on the device (one components pass
@@ -145,6 +145,11 @@ def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None
     "max_job_pixels": ...} of intensity.quantiles_instances_batch's arguments: every result's `quantiles` holds the intensity order
     statistics of its instances (intensity.py: median, quartiles, a 5 % / 95 % range), taken next to measure on the final label map -- one
     launch, one upload and one copy back for all images of one output size.  None adds no launch and no import.
+    texture: None; a uint8 / uint16 [N, h, w, C] array or device tensor at the label maps' size, or a dict {"image": that, "levels": ...,
+    "distance": ..., "channels": ..., "range": ..., "max_job_pixels": ...} of texture.texture_instances_batch's arguments: every result's
+    `texture` holds the co-occurrence matrices of its instances (texture.py: Haralick's features), taken next to quantiles on the final
+    label map -- one launch, one upload and one copy back for all images of one output size (range="object" measures first unless
+    measure= already gave the intensity columns).  None adds no launch and no import.
     split: None; a distance in pixels (a number, 1 .. 64), or a dict of split.split_instances_batch's arguments (distance, connectivity,
     min_seed_area, frame, only): merged instances are then split into their core seeds' regions (split.py), after the clean-up and
     before the expansion and everything else; every result has `parent` set, dets extended by a copy of the parent's row per new id and
@@ -169,6 +174,10 @@ def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None
         from . import intensity
         kw = dict(quantiles) if isinstance(quantiles, dict) else {"image": quantiles}
         intensity.quantiles_instances_batch(out, kw.pop("image", None), **kw)
+    if texture is not None and texture is not False:
+        from . import texture as _texture
+        kw = dict(texture) if isinstance(texture, dict) else {"image": texture}
+        _texture.texture_instances_batch(out, kw.pop("image", None), **kw)
     if neighbours is not None and neighbours is not False:
         from . import neighbours as _neighbours
         _neighbours.neighbours_instances_batch(out, **({} if neighbours is True else dict(neighbours)))

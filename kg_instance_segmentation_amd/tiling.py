@@ -217,8 +217,8 @@ class TiledInstances(Instances):
     """predict_tiled's result: labels = device int32 [H, W] (assemble_host: a NumPy array); dets = float32 [n, 5] (y1, x1, y2, x2, conf) in
     global pixels, clipped to the image, in id order; table = host int64 [n, 8]; masks = None; tile int32 [n]; origin int32 [n, 2];
     tile_masks = the tile-local mask rows in id order (BitMasks; assemble_host: uint8 [n, th, tw]): tile_masks[i] placed at origin[i]
-    is the full mask of instance i + 1.  measurements, neighbours, runs, contours, hulls and quantiles are Instances': None unless asked for
-    (measure=, neighbours=, runs=, contours=, hulls=, quantiles= of predict_tiled).  parent is Instances' too: None unless a split ran
+    is the full mask of instance i + 1.  measurements, neighbours, runs, contours, hulls, quantiles and texture are Instances': None unless
+    asked for (measure=, neighbours=, runs=, contours=, hulls=, quantiles=, texture= of predict_tiled).  parent is Instances' too: None unless a split ran
     (split=, split.py); then dets, tile and origin hold a copy of the parent's row for every new id and tile_masks keeps the rows of the
     parents only: tile_masks[parent[i]] placed at origin[i] is the mask instance i + 1 came from."""
     __slots__ = ("tile", "origin", "tile_masks")
@@ -487,7 +487,7 @@ def assemble(plan, per_tile_preds, nms_thresh=0.5, device=None, stage=None, clea
 
 
 def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thresh=0.5, seg_thresh=0.5, max_workspace_bytes=None, stage=None,
-                  clean=None, measure=False, expand=None, neighbours=None, runs=None, contours=None, hulls=None, quantiles=None, split=None):
+                  clean=None, measure=False, expand=None, neighbours=None, runs=None, contours=None, hulls=None, quantiles=None, split=None, texture=None):
     """Instance segmentation of a whole image at native resolution -> TiledInstances.  image: host uint8 [H, W, 3] (uploaded once, to the
     model's device) or a device uint8 tensor; tile: the network input size, (th, tw) or one int, multiples of 32; overlap: pixels two
     neighbouring tiles share at least (choose it at least as large as the largest object: an object is cut at the edge of the tile that
@@ -512,6 +512,10 @@ def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thres
     then holds the intensity order statistics of the instances (intensity.py: median, quartiles, a 5 % / 95 % range) against the uploaded
     uint8 image, taken next to measure on the final label map -- one more launch, upload and copy back.  None adds no launch and no
     import;
+    texture: None; True, or a dict of texture.texture_instances' keyword arguments (levels, distance, channels, range, max_job_pixels;
+    "image": another uint8 / uint16 [H, W, C] image to take the texture of): the result's `texture` then holds the co-occurrence matrices
+    of the instances (texture.py: Haralick's features) against the uploaded uint8 image, taken next to quantiles on the final label map
+    -- one more launch, upload and copy back.  None adds no launch and no import;
     split: None; a distance in pixels (1 .. 64), or a dict of split.split_instances' arguments (distance, connectivity, min_seed_area,
     frame, only): merged instances of the STITCHED map are then split into their core seeds' regions (split.py, through assemble), after
     the clean-up and before the expansion and everything else; the result has `parent` set, dets / tile / origin extended by a copy of
@@ -519,6 +523,7 @@ def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thres
     import torch
     from . import inference
     quantiles = None if quantiles is False else quantiles
+    texture = None if texture is False else texture
     if int(batch) < 1:
         raise KGLibraryError(f"predict_tiled: batch {batch}")
     mark = stage if stage is not None else (lambda name: None)
@@ -526,7 +531,7 @@ def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thres
         shape, dev = tuple(image.shape), image.device
     else:
         shape, dev = _host_image(image).shape, next(model.parameters()).device
-        if measure or quantiles is not None:                          # the one upload serves the tiles and the measurements
+        if measure or quantiles is not None or texture is not None:   # the one upload serves the tiles and the measurements
             from . import ops
             image = ops.h2d(_host_image(image), dev)
     if len(shape) != 3 or shape[2] != 3:
@@ -548,6 +553,10 @@ def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thres
     if quantiles is not None:
         from . import intensity
         out.quantiles = intensity.quantiles_instances(out, image, **({} if quantiles is True else dict(quantiles)))
+    if texture is not None:
+        from . import texture as _texture
+        kw = {} if texture is True else dict(texture)
+        out.texture = _texture.texture_instances(out, kw.pop("image", image), **kw)
     if neighbours is not None and neighbours is not False:
         from . import neighbours as _neighbours
         out.neighbours = _neighbours.neighbours_instances(out, **({} if neighbours is True else dict(neighbours)))
