@@ -27,7 +27,7 @@ Semantics (include/kgnet_hip.h is the normative text)
 import numpy as np
 
 from . import _lib
-from ._labelmaps import device_maps, host_maps
+from ._labelmaps import device_maps, host_maps, size_batches
 from .instances import Instances, TABLE_COLUMNS  # noqa: F401  (TABLE_COLUMNS: the columns of the tables returned here)
 
 KGLibraryError = _lib.KGLibraryError
@@ -354,7 +354,7 @@ def clean(labels, n, keep="largest", min_area=0, fill_holes=True, max_hole_area=
     return (out[0], tabs[0], old[0]) if relabel else (out[0], tabs[0])
 
 
-def _like(inst, labels, table):
+def like(inst, labels, table):
     """A new object of inst's type with labels and table replaced; dets, the masks and parent (split.py) are kept."""
     from .tiling import TiledInstances
     if isinstance(inst, TiledInstances):
@@ -384,20 +384,15 @@ def clean_instances(inst, **policy):
     else:
         lab = inst.labels.numpy() if torch.is_tensor(inst.labels) else inst.labels
         labels, table = clean_host(lab, len(inst), table=inst.table, **policy)
-    return _like(inst, labels, table)
+    return like(inst, labels, table)
 
 
 def clean_instances_batch(insts, **policy):
     """clean_instances for predict_instances' list (entries may be None): components run ONCE over all images of one output size."""
-    import torch
-    from .inference import size_groups
     _instance_policy("clean", policy)
     out = list(insts)
-    todo = [i for i, v in enumerate(insts) if v is not None]
-    for _, members in size_groups([tuple(insts[i].labels.shape) for i in todo]):
-        idx = [todo[j] for j in members]
-        stack = torch.stack([insts[i].labels for i in idx])
+    for idx, stack, _, _ in size_batches("clean", insts):
         labels, tabs, _ = clean_batch(stack, [len(insts[i]) for i in idx], [insts[i].table for i in idx], **policy)
         for k, i in enumerate(idx):
-            out[i] = _like(insts[i], labels[k], tabs[k])
+            out[i] = like(insts[i], labels[k], tabs[k])
     return out

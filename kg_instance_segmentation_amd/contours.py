@@ -36,12 +36,10 @@ Semantics (include/kgnet_hip.h is the normative text)
 import numpy as np
 
 from . import _lib, _labelmaps, labelmetrics
-from ._labelmaps import is_device
+from ._labelmaps import JOB_COLUMNS as _JOB_COLUMNS, MAX_SIDE, device_stack, host_stack, out_tensor  # noqa: F401  (MAX_SIDE: public here)
 
 KGLibraryError = _lib.KGLibraryError
-MAX_SIDE = 32768
 LDS_BITS = 2 ** 18
-_JOB_COLUMNS = "(img, id, y1, x1, y2, x2)"
 _ROW_JOB_COLUMNS = "(img, id, y1, x1, y2, x2, ring_at, vert_at)"
 
 
@@ -50,13 +48,6 @@ def fits(h, w):
     number of dwords fits 32 KiB of LDS."""
     h, w = int(h), int(w)
     return h > 0 and w > 0 and (h + 2) * 32 * (((w + 2 + 31) // 32) | 1) <= LDS_BITS
-
-
-def _side(fn, maps):
-    H, W = maps.shape[-2:]
-    if H > MAX_SIDE or W > MAX_SIDE:
-        raise KGLibraryError(f"{fn}: a map of {H} x {W} exceeds {MAX_SIDE}")
-    return maps
 
 
 class Contours:
@@ -239,33 +230,17 @@ def _job_rings(lab, H, W, job):
     return _trace_mask(me, y1, x1)
 
 
-def _maps(fn, labels):
-    return _side(fn, _labelmaps.host_maps(fn, labels, True)[0])
-
-
-def _host_job_table(fn, maps, jobs_or_n):
-    from .distance import _job_table
-    if np.ndim(jobs_or_n) == 2 or (np.ndim(jobs_or_n) == 1 and np.size(jobs_or_n) == 0):        # an empty list is no jobs
-        return _job_table(fn, maps, None, jobs_or_n if np.size(jobs_or_n) else np.zeros((0, 6), np.int64), None, None)
-    return _job_table(fn, maps, jobs_or_n, None, None, labelmetrics.label_stats_host)
-
-
 def contours_host(labels, jobs_or_n):
     """labels: integers [H, W] or [nimg, H, W]; jobs_or_n: jobs [m, 6] = (img, id, y1, x1, y2, x2), or the instance count n (one per map
     for a stack): the ids 1 .. n inside their own boxes (labelmetrics.label_stats_host) -> Contours, one row per job.  Never
     size-limited."""
-    maps = _maps("contours_host", labels)
+    maps = host_stack("contours_host", labels)
     nimg, H, W = maps.shape
-    j = _host_job_table("contours_host", maps, jobs_or_n)
+    j = _labelmaps.host_job_table("contours_host", maps, jobs_or_n, labelmetrics.label_stats_host)
     return _assemble([_job_rings(maps[i], H, W, rest) if 0 <= i < nimg else _EMPTY for i, *rest in j.tolist()])
 
 
 # ---- device -----------------------------------------------------------------------------------------------------------------------------
-
-def _device_maps(fn, t):
-    t = _labelmaps.device_maps(fn, t, True)
-    return _side(fn, t.view((-1,) + t.shape[-2:]))
-
 
 def contour_counts(labels, jobs):
     """kg_label_contour_counts as it is: labels device int32 [H, W] or [nimg, H, W]; jobs host integers [m, 6] = (img, id, y1, x1, y2, x2)
@@ -273,7 +248,7 @@ def contour_counts(labels, jobs):
     fit the device route (fits) and the counts are 0.  One launch, no copy back, no synchronisation."""
     import torch
     from ._lib import ptr, stream_ptr
-    lab = _device_maps("contour_counts", labels)
+    lab = device_stack("contour_counts", labels)[0]
     nimg, H, W = lab.shape
     jd = _labelmaps.device_jobs("contour_counts", jobs, 6, _JOB_COLUMNS, lab.device)
     m = jd.shape[0]
@@ -283,12 +258,6 @@ def contour_counts(labels, jobs):
     return out
 
 
-def _out(fn, what, t, shape, dtype, dev):
-    if not is_device(t) or t.dtype != dtype or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
-        raise KGLibraryError(f"{fn}: {what} must be a contiguous {str(dtype).replace('torch.', '')} {list(shape)} tensor on the maps' device")
-    return t
-
-
 def contour_rows(labels, jobs, R, V, rings=None, verts=None):
     """kg_label_contours as it is: jobs host integers [m, 8] = (img, id, y1, x1, y2, x2, ring_at, vert_at) (uploaded once) or a device
     int32 tensor -> (rings device int64 [R, 4] = {first, count, perimeter, area2}, verts device int32 [V, 2] = (y, x)).  rings / verts:
@@ -296,15 +265,15 @@ def contour_rows(labels, jobs, R, V, rings=None, verts=None):
     no copy back, no synchronisation."""
     import torch
     from ._lib import ptr, stream_ptr
-    lab = _device_maps("contour_rows", labels)
+    lab = device_stack("contour_rows", labels)[0]
     nimg, H, W = lab.shape
     jd = _labelmaps.device_jobs("contour_rows", jobs, 8, _ROW_JOB_COLUMNS, lab.device)
     m = jd.shape[0]
     R, V = int(R), int(V)
     if not 0 <= R <= 2 ** 31 - 1 or not 0 <= V <= 2 ** 31 - 1:
         raise KGLibraryError(f"contour_rows: R {R}, V {V}")
-    rings = torch.zeros(R, 4, dtype=torch.int64, device=lab.device) if rings is None else _out("contour_rows", "rings", rings, (R, 4), torch.int64, lab.device)
-    verts = torch.zeros(V, 2, dtype=torch.int32, device=lab.device) if verts is None else _out("contour_rows", "verts", verts, (V, 2), torch.int32, lab.device)
+    rings = torch.zeros(R, 4, dtype=torch.int64, device=lab.device) if rings is None else out_tensor("contour_rows", "rings", rings, (R, 4), torch.int64, lab.device)
+    verts = torch.zeros(V, 2, dtype=torch.int32, device=lab.device) if verts is None else out_tensor("contour_rows", "verts", verts, (V, 2), torch.int32, lab.device)
     with torch.cuda.device(lab.device):
         _lib.call("kg_label_contours", ptr(lab), nimg, H, W, ptr(jd) if m else None, m, ptr(rings) if R else None, R, ptr(verts) if V else None, V,
                   stream_ptr())
@@ -359,36 +328,22 @@ def contours(labels, n=None, jobs=None, stats=None):
     ONE kg_label_contour_counts launch and one small copy back, a host prefix over rings and vertices, ONE kg_label_contours launch and
     one copy back.  A job whose box does not fit the device route (fits) is traced by the host tracer on its box, sliced from the device
     map and copied back alone."""
-    from .distance import _job_table
-    lab = _device_maps("contours", labels)
-    return _device_contours(lab, _job_table("contours", lab, n, jobs, stats, labelmetrics.label_stats))
+    lab = device_stack("contours", labels)[0]
+    return _device_contours(lab, _labelmaps.job_table("contours", lab, n, jobs, stats, labelmetrics.label_stats))
 
 
 # ---- Instances ----------------------------------------------------------------------------------------------------------------------------
 
 def _instance_contours(insts):
     """-> one Contours per entry (None for a None entry); the entries themselves are not touched"""
-    import torch
-    from . import distance
-    from .inference import size_groups
     out = [None] * len(insts)
-    todo = [i for i, v in enumerate(insts) if v is not None]
-    for i in todo:
-        distance._check_instances("contours_instances", insts[i])
-    host = [i for i in todo if not is_device(insts[i].labels)]
-    for i in host:
-        lab = insts[i].labels.numpy() if torch.is_tensor(insts[i].labels) else np.asarray(insts[i].labels)
-        out[i] = contours_host(lab, _labelmaps.instance_jobs(insts[i], 0, 0, *lab.shape))
-    todo = [i for i in todo if i not in host]
-    for (H, W), members in size_groups([tuple(insts[i].labels.shape) for i in todo]):
-        idx = [todo[k] for k in members]
-        stack = insts[idx[0]].labels[None] if len(idx) == 1 else torch.stack([insts[i].labels for i in idx])
-        got = _device_contours(_device_maps("contours_instances", stack),
-                               np.concatenate([_labelmaps.instance_jobs(insts[i], k, 0, H, W) for k, i in enumerate(idx)]))
-        r = 0
-        for i in idx:
-            out[i] = got.slice(r, r + len(insts[i]))
-            r += len(insts[i])
+
+    def host_one(i, inst, lab):
+        out[i] = contours_host(lab, _labelmaps.instance_jobs(inst, 0, 0, *lab.shape))
+    for idx, stack, H, W in _labelmaps.size_batches("contours_instances", insts, host_one):
+        got = _device_contours(device_stack("contours_instances", stack)[0], _labelmaps.batch_jobs(insts, idx, 0, H, W))
+        for i, a, b in _labelmaps.deal(insts, idx):
+            out[i] = got.slice(a, b)
     return out
 
 

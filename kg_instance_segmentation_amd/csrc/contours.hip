@@ -32,7 +32,6 @@
 // prefix counts, each inside a 64-bit unsigned range predicate (slot < R, first + k < V).  No atomics.
 #include "label_common.h"
 
-#define KG_CT_MAX_SIDE 32768            // H, W <= 2^15 as in measure.hip
 #define KG_CT_BITS (1 << 18)            // membership bits of one job, halo included: 32 KB of LDS
 
 // pitch in bits of a box of w columns: w + 2 rounded up to an odd number of dwords
@@ -171,27 +170,13 @@ __global__ __launch_bounds__(256) void label_contours_kernel(const int* __restri
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------
-static inline bool kg_ct_apart(const void* a, long abytes, const void* b, long bbytes) {
-    const char* pa = (const char*)a; const char* pb = (const char*)b;
-    return pa + abytes <= pb || pb + bbytes <= pa;
-}
-static int kg_ct_check(const char* fn, const int* labels, int nimg, int H, int W, const int* jobs, int m) {
-    KG_CHECK_ARG(nimg > 0 && H > 0 && W > 0 && m >= 0, "%s: bad size (nimg %d, H %d, W %d, m %d)", fn, nimg, H, W, m);
-    KG_CHECK_ARG(H <= KG_CT_MAX_SIDE && W <= KG_CT_MAX_SIDE, "%s: H %d, W %d exceed %d", fn, H, W, KG_CT_MAX_SIDE);
-    KG_TRY(kg_check_stack_size(fn, nimg, H, W));
-    KG_CHECK_ARG(labels, "%s: null pointer (labels)", fn);
-    KG_CHECK_ARG(jobs || m == 0, "%s: null pointer (jobs)", fn);
-    KG_CHECK_ARG(kg_aligned(labels, 3) && kg_aligned(jobs, 3), "%s: misaligned pointer", fn);
-    return KG_OK;
-}
-
 // labels: device int32 [nimg][H][W]; jobs: device int32 [m][6] = (img, id, y1, x1, y2, x2), written by the caller;
 // out: device int64 [m][4] = {rings, vertices, perimeter, status}
 extern "C" int kg_label_contour_counts(const int* labels, int nimg, int H, int W, const int* jobs, int m, long long* out, void* stream) {
-    KG_TRY(kg_ct_check("kg_label_contour_counts", labels, nimg, H, W, jobs, m));
+    KG_TRY(kg_check_job_stack("kg_label_contour_counts", labels, nimg, H, W, jobs, m));
     KG_CHECK_ARG(out || m == 0, "kg_label_contour_counts: null pointer (out)");
     KG_CHECK_ARG(kg_aligned(out, 7), "kg_label_contour_counts: misaligned pointer");
-    KG_CHECK_ARG(!out || kg_ct_apart(out, 32L * m, labels, 4L * nimg * H * W), "kg_label_contour_counts: out aliases labels");
+    KG_CHECK_ARG(!out || kg_apart(out, 32L * m, labels, 4L * nimg * H * W), "kg_label_contour_counts: out aliases labels");
     if (m == 0) return KG_OK;
     hipLaunchKernelGGL(label_contours_kernel<false>, dim3(kg_grid_cap(m)), dim3(256), 0, (hipStream_t)stream, labels, nimg, H, W, jobs, m, out,
                        0LL, (int*)nullptr, 0LL);
@@ -204,15 +189,15 @@ extern "C" int kg_label_contour_counts(const int* labels, int nimg, int H, int W
 extern "C" int kg_label_contours(const int* labels, int nimg, int H, int W, const int* jobs, int m, long long* rings, int R, int* verts, int V,
                                  void* stream) {
     const char* fn = "kg_label_contours";
-    KG_TRY(kg_ct_check(fn, labels, nimg, H, W, jobs, m));
+    KG_TRY(kg_check_job_stack(fn, labels, nimg, H, W, jobs, m));
     KG_CHECK_ARG(R >= 0 && V >= 0, "%s: R %d, V %d", fn, R, V);
     KG_CHECK_ARG(rings || R == 0, "%s: null pointer (rings)", fn);
     KG_CHECK_ARG(verts || V == 0, "%s: null pointer (verts)", fn);
     KG_CHECK_ARG(kg_aligned(rings, 7) && kg_aligned(verts, 3), "%s: misaligned pointer", fn);
     const long lbytes = 4L * nimg * H * W;
-    KG_CHECK_ARG(!rings || kg_ct_apart(rings, 32L * R, labels, lbytes), "%s: rings aliases labels", fn);
-    KG_CHECK_ARG(!verts || kg_ct_apart(verts, 8L * V, labels, lbytes), "%s: verts aliases labels", fn);
-    KG_CHECK_ARG(!rings || !verts || kg_ct_apart(rings, 32L * R, verts, 8L * V), "%s: rings aliases verts", fn);
+    KG_CHECK_ARG(!rings || kg_apart(rings, 32L * R, labels, lbytes), "%s: rings aliases labels", fn);
+    KG_CHECK_ARG(!verts || kg_apart(verts, 8L * V, labels, lbytes), "%s: verts aliases labels", fn);
+    KG_CHECK_ARG(!rings || !verts || kg_apart(rings, 32L * R, verts, 8L * V), "%s: rings aliases verts", fn);
     if (m == 0 || (R == 0 && V == 0)) return KG_OK;                    // no slot passes a predicate: nothing to store
     hipLaunchKernelGGL(label_contours_kernel<true>, dim3(kg_grid_cap(m)), dim3(256), 0, (hipStream_t)stream, labels, nimg, H, W, jobs, m, rings,
                        (long long)R, verts, (long long)V);

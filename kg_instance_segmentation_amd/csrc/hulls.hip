@@ -33,7 +33,6 @@
 // address depends on a label.
 #include "label_common.h"
 
-#define KG_HL_MAX_SIDE 32768            // H, W <= 2^15 as in measure.hip: a box-local x fits 16 bits
 #define KG_HL_LINES 4096                // lattice lines of one job: a box of at most 4095 rows
 
 // edge a is narrower than edge b: c_a^2 / d_a < c_b^2 / d_b, a tie to the smaller k; k < 0 is "no edge".  c < 2^31 and d < 2^32, so
@@ -254,29 +253,22 @@ __global__ __launch_bounds__(256) void label_hulls_kernel(const int* __restrict_
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------
-static inline bool kg_hl_apart(const void* a, long abytes, const void* b, long bbytes) {
-    const char* pa = (const char*)a; const char* pb = (const char*)b;
-    return pa + abytes <= pb || pb + bbytes <= pa;
-}
-
 // labels: device int32 [nimg][H][W]; jobs: device int32 [m][8] = (img, id, y1, x1, y2, x2, vert_at, cap), written by the caller;
 // rows: device int64 [m][10]; verts: device int32 [V][2] = (y, x)
 extern "C" int kg_label_hulls(const int* labels, int nimg, int H, int W, const int* jobs, int m, long long* rows, int* verts, int V,
                               void* stream) {
     const char* fn = "kg_label_hulls";
-    KG_CHECK_ARG(nimg > 0 && H > 0 && W > 0 && m >= 0 && V >= 0, "%s: bad size (nimg %d, H %d, W %d, m %d, V %d)", fn, nimg, H, W, m, V);
-    KG_CHECK_ARG(H <= KG_HL_MAX_SIDE && W <= KG_HL_MAX_SIDE, "%s: H %d, W %d exceed %d", fn, H, W, KG_HL_MAX_SIDE);
-    KG_TRY(kg_check_stack_size(fn, nimg, H, W));
-    KG_CHECK_ARG(labels, "%s: null pointer (labels)", fn);
-    KG_CHECK_ARG((jobs && rows) || m == 0, "%s: null pointer (jobs / rows)", fn);
+    KG_TRY(kg_check_job_stack(fn, labels, nimg, H, W, jobs, m));       // H, W <= KG_LABEL_MAX_SIDE: a box-local x fits the 16 bits of a packed vertex
+    KG_CHECK_ARG(V >= 0, "%s: bad size (V %d)", fn, V);
+    KG_CHECK_ARG(rows || m == 0, "%s: null pointer (rows)", fn);
     KG_CHECK_ARG(verts || V == 0, "%s: null pointer (verts)", fn);
-    KG_CHECK_ARG(kg_aligned(labels, 3) && kg_aligned(jobs, 3) && kg_aligned(rows, 7) && kg_aligned(verts, 3), "%s: misaligned pointer", fn);
+    KG_CHECK_ARG(kg_aligned(rows, 7) && kg_aligned(verts, 3), "%s: misaligned pointer", fn);
     const long lbytes = 4L * nimg * H * W;
-    KG_CHECK_ARG(!rows || kg_hl_apart(rows, 80L * m, labels, lbytes), "%s: rows aliases labels", fn);
-    KG_CHECK_ARG(!verts || kg_hl_apart(verts, 8L * V, labels, lbytes), "%s: verts aliases labels", fn);
-    KG_CHECK_ARG(!rows || !verts || kg_hl_apart(rows, 80L * m, verts, 8L * V), "%s: rows aliases verts", fn);
-    KG_CHECK_ARG(!rows || !jobs || kg_hl_apart(rows, 80L * m, jobs, 32L * m), "%s: rows aliases jobs", fn);
-    KG_CHECK_ARG(!verts || !jobs || kg_hl_apart(verts, 8L * V, jobs, 32L * m), "%s: verts aliases jobs", fn);
+    KG_CHECK_ARG(!rows || kg_apart(rows, 80L * m, labels, lbytes), "%s: rows aliases labels", fn);
+    KG_CHECK_ARG(!verts || kg_apart(verts, 8L * V, labels, lbytes), "%s: verts aliases labels", fn);
+    KG_CHECK_ARG(!rows || !verts || kg_apart(rows, 80L * m, verts, 8L * V), "%s: rows aliases verts", fn);
+    KG_CHECK_ARG(!rows || !jobs || kg_apart(rows, 80L * m, jobs, 32L * m), "%s: rows aliases jobs", fn);
+    KG_CHECK_ARG(!verts || !jobs || kg_apart(verts, 8L * V, jobs, 32L * m), "%s: verts aliases jobs", fn);
     if (m == 0) return KG_OK;
     hipLaunchKernelGGL(label_hulls_kernel, dim3(kg_grid_cap(m)), dim3(256), 0, (hipStream_t)stream, labels, nimg, H, W, jobs, m, rows, verts,
                        (long long)V);

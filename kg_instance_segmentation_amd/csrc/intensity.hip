@@ -15,7 +15,6 @@
 // at fixed positions and only compared and multiplied (a row with den <= 0, num < 0 or num > den is not divided by: lo = hi = 0).
 #include "label_common.h"
 
-#define KG_IQ_MAX_SIDE 32768            // as measure.hip: a box holds at most 2^30 pixels, so every count and rank fits int32
 #define KG_IQ_MAX_Q 8                   // quantiles per call: 16 ranks per channel
 #define KG_IQ_RANKS (2 * KG_IQ_MAX_Q)
 #define KG_IQ_DEN_MAX 1000000           // num (n - 1) < 2^20 2^30: the 64-bit product cannot overflow
@@ -224,16 +223,10 @@ static void iq_launch(const int* labels, int nimg, int H, int W, const void* ima
 // the checks both entries share; fn = the entry's name
 static int iq_check(const char* fn, const int* labels, int nimg, int H, int W, const void* image, int channels, int elem_bytes, const int* jobs,
                     int m, const int* out) {
-    KG_CHECK_ARG(nimg > 0 && H > 0 && W > 0 && m >= 0, "%s: bad size (nimg %d, H %d, W %d, m %d)", fn, nimg, H, W, m);
-    KG_CHECK_ARG(H <= KG_IQ_MAX_SIDE && W <= KG_IQ_MAX_SIDE, "%s: H %d, W %d exceed %d (the bound that keeps every count inside int32)", fn, H, W,
-                 KG_IQ_MAX_SIDE);
-    KG_TRY(kg_check_stack_size(fn, nimg, H, W));
-    KG_CHECK_ARG(channels >= 1 && channels <= 4, "%s: channels %d (1 .. 4)", fn, channels);
-    KG_CHECK_ARG(elem_bytes == 1 || elem_bytes == 2, "%s: elem_bytes %d (1 or 2)", fn, elem_bytes);
-    KG_CHECK_ARG(labels && image, "%s: null pointer (labels / image)", fn);
-    KG_CHECK_ARG((jobs && out) || m == 0, "%s: null pointer (jobs / out)", fn);
-    KG_CHECK_ARG(kg_aligned(labels, 3) && kg_aligned(jobs, 3) && kg_aligned(out, 3) && kg_aligned(image, elem_bytes == 2 ? 1 : 0),
-                 "%s: misaligned pointer", fn);
+    KG_TRY(kg_check_job_stack(fn, labels, nimg, H, W, jobs, m));       // H, W <= KG_LABEL_MAX_SIDE: every count and rank of a box fits int32
+    KG_TRY(kg_check_image(fn, image, channels, elem_bytes));
+    KG_CHECK_ARG(out || m == 0, "%s: null pointer (out)", fn);
+    KG_CHECK_ARG(kg_aligned(out, 3), "%s: misaligned pointer", fn);
     return KG_OK;
 }
 

@@ -1,7 +1,9 @@
-// label_common.h -- what the label-map kernels share (instances.hip, tiling.hip, labelmetrics.hip, components.hip, measure.hip, intensity.hip, split.hip, texture.hip; paste.hip for
-// the bit-mask leading dimension): wave reductions, the clamped job box and its walk, the block combine of four wave partials, the
-// row-segment run walk, per-image ranges passed by value, and the host argument checks.  Integers only, plain C++ and vector memory
-// operations only.
+// label_common.h -- what the label-map kernels share (instances.hip, tiling.hip, labelmetrics.hip, components.hip, measure.hip,
+// distance.hip, neighbours.hip, runlengths.hip, contours.hip, polygons.hip, hulls.hip, intensity.hip, split.hip, texture.hip; paste.hip
+// for the bit-mask leading dimension): wave reductions, the clamped job box and its walk, the block combine of four wave partials, the
+// row-segment run walk, per-image ranges passed by value, and the host argument checks -- among them the side bound KG_LABEL_MAX_SIDE,
+// the block that opens a per-job entry (kg_check_job_stack), the image check (kg_check_image) and the overlap test (kg_apart).
+// Integers only, plain C++ and vector memory operations only.
 //
 // INDEX RULE of the family.  Every entry validates on the host before any HIP call and never synchronises; the number of launches does
 // not depend on a count read from the device; every output element is written.  No address in a kernel depends on a value read from
@@ -159,6 +161,32 @@ static inline int kg_check_stack_size(const char* fn, int nimg, int H, int W) {
     return KG_OK;
 }
 static inline bool kg_aligned(const void* p, unsigned mask) { return ((unsigned long long)(size_t)p & mask) == 0; }
+// the byte ranges [a, a + abytes) and [b, b + bbytes) do not overlap; an absent or empty range overlaps nothing
+static inline bool kg_apart(const void* a, long abytes, const void* b, long bbytes) {
+    const char* pa = (const char*)a; const char* pb = (const char*)b;
+    return !a || !b || abytes == 0 || bbytes == 0 || pa + abytes <= pb || pb + bbytes <= pa;
+}
+// The side bound of every per-job entry: H, W <= 2^15, so a box holds at most 2^30 pixels.  Each file says what it relies on.
+#define KG_LABEL_MAX_SIDE 32768
+// what opens a job entry: a stack of nimg int32 maps [H][W] within the side bound and 2^31 - 1 pixels, and a job table of m rows
+// (NULL only when m == 0), both 4-byte aligned.  An extra size (R, V), the outputs and their aliasing stay with the entry.
+static inline int kg_check_job_stack(const char* fn, const int* labels, int nimg, int H, int W, const int* jobs, int m) {
+    KG_CHECK_ARG(nimg > 0 && H > 0 && W > 0 && m >= 0, "%s: bad size (nimg %d, H %d, W %d, m %d)", fn, nimg, H, W, m);
+    KG_CHECK_ARG(H <= KG_LABEL_MAX_SIDE && W <= KG_LABEL_MAX_SIDE, "%s: H %d, W %d exceed %d", fn, H, W, KG_LABEL_MAX_SIDE);
+    KG_TRY(kg_check_stack_size(fn, nimg, H, W));
+    KG_CHECK_ARG(labels, "%s: null pointer (labels)", fn);
+    KG_CHECK_ARG(jobs || m == 0, "%s: null pointer (jobs)", fn);
+    KG_CHECK_ARG(kg_aligned(labels, 3) && kg_aligned(jobs, 3), "%s: misaligned pointer", fn);
+    return KG_OK;
+}
+// the image of an entry that reads pixel values: [nimg][H][W][channels] of 1- or 2-byte elements, aligned to its element
+static inline int kg_check_image(const char* fn, const void* image, int channels, int elem_bytes) {
+    KG_CHECK_ARG(channels >= 1 && channels <= 4, "%s: channels %d (1 .. 4)", fn, channels);
+    KG_CHECK_ARG(elem_bytes == 1 || elem_bytes == 2, "%s: elem_bytes %d (1 or 2)", fn, elem_bytes);
+    KG_CHECK_ARG(image, "%s: null pointer (image)", fn);
+    KG_CHECK_ARG(kg_aligned(image, elem_bytes == 2 ? 1 : 0), "%s: misaligned pointer (image)", fn);
+    return KG_OK;
+}
 // grid cap of the kernels that stride over what is left
 #define KG_LABEL_MAX_BLOCKS (1 << 20)
 static inline unsigned kg_grid_cap(long blocks) { return (unsigned)(blocks < KG_LABEL_MAX_BLOCKS ? blocks : KG_LABEL_MAX_BLOCKS); }

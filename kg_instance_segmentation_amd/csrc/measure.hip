@@ -10,8 +10,6 @@
 // exists.  No atomics.
 #include "label_common.h"
 
-#define KG_MS_MAX_SIDE 32768            // H, W <= 2^15: area <= 2^30, a coordinate product < 2^30, a coordinate sum < 2^60, and a uint16
-                                        // sum of squares < 2^62 -- every column fits int64 and nothing else needs checking
 #define KG_MS_GEOM 10                   // geometry columns; 4 more per channel
 #define KG_MS_MAX_COLS (KG_MS_GEOM + 4 * 4)
 
@@ -128,17 +126,14 @@ static void ms_launch(const int* labels, int nimg, int H, int W, const void* ima
 // == 0; jobs: device int32 [m][6] = (img, id, y1, x1, y2, x2), written by the caller; out: device int64 [m][10 + 4 * channels]
 extern "C" int kg_label_measure(const int* labels, int nimg, int H, int W, const void* image, int channels, int elem_bytes, const int* jobs, int m,
                                 long long* out, void* stream) {
-    KG_CHECK_ARG(nimg > 0 && H > 0 && W > 0 && m >= 0, "kg_label_measure: bad size (nimg %d, H %d, W %d, m %d)", nimg, H, W, m);
-    KG_CHECK_ARG(H <= KG_MS_MAX_SIDE && W <= KG_MS_MAX_SIDE, "kg_label_measure: H %d, W %d exceed %d (the bound that keeps every sum inside int64)", H, W,
-                 KG_MS_MAX_SIDE);
-    KG_TRY(kg_check_stack_size("kg_label_measure", nimg, H, W));
+    // H, W <= KG_LABEL_MAX_SIDE (2^15): area <= 2^30, a coordinate product < 2^30, a coordinate sum < 2^60, and a uint16 sum of squares
+    // < 2^62 -- every column fits int64 and nothing else needs checking
+    KG_TRY(kg_check_job_stack("kg_label_measure", labels, nimg, H, W, jobs, m));
     KG_CHECK_ARG(channels >= 0 && channels <= 4, "kg_label_measure: channels %d (0 .. 4)", channels);
     KG_CHECK_ARG(elem_bytes == 1 || elem_bytes == 2, "kg_label_measure: elem_bytes %d (1 or 2)", elem_bytes);
-    KG_CHECK_ARG(labels, "kg_label_measure: null pointer (labels)");
     KG_CHECK_ARG((image != nullptr) == (channels > 0), "kg_label_measure: image must be NULL exactly when channels == 0 (channels %d)", channels);
-    KG_CHECK_ARG((jobs && out) || m == 0, "kg_label_measure: null pointer (jobs / out)");
-    KG_CHECK_ARG(kg_aligned(labels, 3) && kg_aligned(jobs, 3) && kg_aligned(out, 7) && kg_aligned(image, elem_bytes == 2 ? 1 : 0),
-                 "kg_label_measure: misaligned pointer");
+    KG_CHECK_ARG(out || m == 0, "kg_label_measure: null pointer (out)");
+    KG_CHECK_ARG(kg_aligned(out, 7) && kg_aligned(image, elem_bytes == 2 ? 1 : 0), "kg_label_measure: misaligned pointer");
     if (m == 0) return KG_OK;
     hipStream_t s = (hipStream_t)stream;
     switch (channels * 2 + (elem_bytes == 2)) {

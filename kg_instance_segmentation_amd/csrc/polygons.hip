@@ -33,7 +33,6 @@
 #define KG_POLY_TILE_H 32
 #define KG_POLY_TILE_W 64
 #define KG_POLY_EDGE_CHUNK 256          // edges staged per barrier: one per thread
-#define KG_POLY_MAX_SIDE 32768          // H, W <= 2^15 as in measure.hip: a centre coordinate stays below 2^23 + 2^7
 #define KG_POLY_ROWS (KG_POLY_TILE_H / 4)
 
 static_assert(KG_POLY_TILE_W == 64 && KG_POLY_TILE_H % 4 == 0 && KG_POLY_ROWS <= 32 && KG_POLY_EDGE_CHUNK == 256,
@@ -133,11 +132,6 @@ __global__ __launch_bounds__(256) void polygons_fill_kernel(const int4* __restri
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------
-static inline bool kg_poly_apart(const void* a, long abytes, const void* b, long bbytes) {
-    const char* pa = (const char*)a; const char* pb = (const char*)b;
-    return !a || !b || abytes == 0 || bbytes == 0 || pa + abytes <= pb || pb + bbytes <= pa;
-}
-
 // edges: device int32 [E][4] = (x0, y0, x1, y1); items: device int32 [n_items][4] = {value, edge_first, edge_count, row}; tile_ptr: device
 // int32 [nimg * tiles + 1], tiles = ceil(H / KG_POLY_TILE_H) * ceil(W / KG_POLY_TILE_W); out, cover: device int32 [nimg][H][W]
 extern "C" int kg_polygons_fill(const int* edges, int E, const int* items, int n_items, const int* tile_ptr, int nimg, int H, int W, int background,
@@ -145,7 +139,8 @@ extern "C" int kg_polygons_fill(const int* edges, int E, const int* items, int n
     const char* fn = "kg_polygons_fill";
     KG_CHECK_ARG(nimg > 0 && H > 0 && W > 0, "%s: bad size (nimg %d, H %d, W %d)", fn, nimg, H, W);
     KG_CHECK_ARG(E >= 0 && n_items >= 0, "%s: E %d, n_items %d", fn, E, n_items);
-    KG_CHECK_ARG(H <= KG_POLY_MAX_SIDE && W <= KG_POLY_MAX_SIDE, "%s: H %d, W %d exceed %d", fn, H, W, KG_POLY_MAX_SIDE);
+    // H, W <= 2^15: a centre coordinate stays below 2^23 + 2^7
+    KG_CHECK_ARG(H <= KG_LABEL_MAX_SIDE && W <= KG_LABEL_MAX_SIDE, "%s: H %d, W %d exceed %d", fn, H, W, KG_LABEL_MAX_SIDE);
     KG_TRY(kg_check_stack_size(fn, nimg, H, W));
     KG_CHECK_ARG(out, "%s: null pointer (out)", fn);
     KG_CHECK_ARG(tile_ptr, "%s: null pointer (tile_ptr)", fn);
@@ -156,11 +151,11 @@ extern "C" int kg_polygons_fill(const int* edges, int E, const int* items, int n
     const int tiles_y = (H + KG_POLY_TILE_H - 1) / KG_POLY_TILE_H, tiles_x = (W + KG_POLY_TILE_W - 1) / KG_POLY_TILE_W;
     const long ntiles = (long)nimg * tiles_y * tiles_x;                // <= nimg * H * W <= 2^31 - 1
     const long mbytes = 4L * nimg * H * W, ebytes = 16L * E, ibytes = 16L * n_items, pbytes = 4L * (ntiles + 1);
-    KG_CHECK_ARG(kg_poly_apart(out, mbytes, cover, mbytes), "%s: out aliases cover", fn);
-    KG_CHECK_ARG(kg_poly_apart(out, mbytes, edges, ebytes) && kg_poly_apart(out, mbytes, items, ibytes) && kg_poly_apart(out, mbytes, tile_ptr, pbytes),
+    KG_CHECK_ARG(kg_apart(out, mbytes, cover, mbytes), "%s: out aliases cover", fn);
+    KG_CHECK_ARG(kg_apart(out, mbytes, edges, ebytes) && kg_apart(out, mbytes, items, ibytes) && kg_apart(out, mbytes, tile_ptr, pbytes),
                  "%s: out aliases a table", fn);
-    KG_CHECK_ARG(kg_poly_apart(cover, mbytes, edges, ebytes) && kg_poly_apart(cover, mbytes, items, ibytes) &&
-                     kg_poly_apart(cover, mbytes, tile_ptr, pbytes), "%s: cover aliases a table", fn);
+    KG_CHECK_ARG(kg_apart(cover, mbytes, edges, ebytes) && kg_apart(cover, mbytes, items, ibytes) &&
+                     kg_apart(cover, mbytes, tile_ptr, pbytes), "%s: cover aliases a table", fn);
     const dim3 grid(kg_grid_cap(ntiles));
     if (cover)
         hipLaunchKernelGGL(polygons_fill_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, (const int4*)edges, (unsigned long long)E,

@@ -18,7 +18,6 @@
 // No atomics anywhere.
 #include "label_common.h"
 
-#define KG_RL_MAX_SIDE 32768            // H, W <= 2^15 as in measure.hip: a box holds <= 2^30 pixels, hence <= 2^30 runs
 #define KG_RL_BITS (1 << 17)            // membership bits of one tile of a box: 16 KB of LDS
 
 // A box of h rows is walked in tiles of cw columns; a tile keeps one membership bit per pixel of its h rows plus the row of the pixels
@@ -157,27 +156,14 @@ __global__ __launch_bounds__(256) void runs_paint_kernel(const int* __restrict__
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------
-static inline bool kg_rl_apart(const void* a, long abytes, const void* b, long bbytes) {
-    const char* pa = (const char*)a; const char* pb = (const char*)b;
-    return pa + abytes <= pb || pb + bbytes <= pa;
-}
-static int kg_rl_check(const char* fn, const int* labels, int nimg, int H, int W, const int* jobs, int m) {
-    KG_CHECK_ARG(nimg > 0 && H > 0 && W > 0 && m >= 0, "%s: bad size (nimg %d, H %d, W %d, m %d)", fn, nimg, H, W, m);
-    KG_CHECK_ARG(H <= KG_RL_MAX_SIDE && W <= KG_RL_MAX_SIDE, "%s: H %d, W %d exceed %d", fn, H, W, KG_RL_MAX_SIDE);
-    KG_TRY(kg_check_stack_size(fn, nimg, H, W));
-    KG_CHECK_ARG(labels, "%s: null pointer (labels)", fn);
-    KG_CHECK_ARG(jobs || m == 0, "%s: null pointer (jobs)", fn);
-    KG_CHECK_ARG(kg_aligned(labels, 3) && kg_aligned(jobs, 3), "%s: misaligned pointer", fn);
-    return KG_OK;
-}
-
+// (H, W <= KG_LABEL_MAX_SIDE: a box holds <= 2^30 pixels, hence <= 2^30 runs)
 // labels: device int32 [nimg][H][W]; jobs: device int32 [m][6] = (img, id, y1, x1, y2, x2), written by the caller;
 // out: device int32 [m][2] = {heads, tails}
 extern "C" int kg_label_run_counts(const int* labels, int nimg, int H, int W, const int* jobs, int m, int* out, void* stream) {
-    KG_TRY(kg_rl_check("kg_label_run_counts", labels, nimg, H, W, jobs, m));
+    KG_TRY(kg_check_job_stack("kg_label_run_counts", labels, nimg, H, W, jobs, m));
     KG_CHECK_ARG(out || m == 0, "kg_label_run_counts: null pointer (out)");
     KG_CHECK_ARG(kg_aligned(out, 3), "kg_label_run_counts: misaligned pointer");
-    KG_CHECK_ARG(!out || kg_rl_apart(out, 8L * m, labels, 4L * nimg * H * W), "kg_label_run_counts: out aliases labels");
+    KG_CHECK_ARG(!out || kg_apart(out, 8L * m, labels, 4L * nimg * H * W), "kg_label_run_counts: out aliases labels");
     if (m == 0) return KG_OK;
     hipLaunchKernelGGL(label_runs_kernel<false>, dim3(kg_grid_cap(m)), dim3(256), 0, (hipStream_t)stream, labels, nimg, H, W, jobs, m, out, 0LL);
     KG_CHECK_LAUNCH("label_run_counts");
@@ -186,11 +172,11 @@ extern "C" int kg_label_run_counts(const int* labels, int nimg, int H, int W, co
 
 // jobs: device int32 [m][8] = (img, id, y1, x1, y2, x2, head_at, tail_at); out: device int32 [R][2] = {first, last}
 extern "C" int kg_label_runs(const int* labels, int nimg, int H, int W, const int* jobs, int m, int* out, int R, void* stream) {
-    KG_TRY(kg_rl_check("kg_label_runs", labels, nimg, H, W, jobs, m));
+    KG_TRY(kg_check_job_stack("kg_label_runs", labels, nimg, H, W, jobs, m));
     KG_CHECK_ARG(R >= 0, "kg_label_runs: R %d", R);
     KG_CHECK_ARG(out || R == 0, "kg_label_runs: null pointer (out)");
     KG_CHECK_ARG(kg_aligned(out, 3), "kg_label_runs: misaligned pointer");
-    KG_CHECK_ARG(!out || kg_rl_apart(out, 8L * R, labels, 4L * nimg * H * W), "kg_label_runs: out aliases labels");
+    KG_CHECK_ARG(!out || kg_apart(out, 8L * R, labels, 4L * nimg * H * W), "kg_label_runs: out aliases labels");
     if (m == 0 || R == 0) return KG_OK;                                // no slot passes the predicate: nothing to store
     hipLaunchKernelGGL(label_runs_kernel<true>, dim3(kg_grid_cap(m)), dim3(256), 0, (hipStream_t)stream, labels, nimg, H, W, jobs, m, out,
                        (long long)R);
@@ -201,12 +187,12 @@ extern "C" int kg_label_runs(const int* labels, int nimg, int H, int W, const in
 // runs: device int32 [R][3] = {first, last, value}, sorted by first and disjoint (the caller's promise); out: device int32 [H][W]
 extern "C" int kg_runs_paint(const int* runs, int R, int H, int W, int background, int* out, void* stream) {
     KG_CHECK_ARG(H > 0 && W > 0 && R >= 0, "kg_runs_paint: bad size (R %d, H %d, W %d)", R, H, W);
-    KG_CHECK_ARG(H <= KG_RL_MAX_SIDE && W <= KG_RL_MAX_SIDE, "kg_runs_paint: H %d, W %d exceed %d", H, W, KG_RL_MAX_SIDE);
+    KG_CHECK_ARG(H <= KG_LABEL_MAX_SIDE && W <= KG_LABEL_MAX_SIDE, "kg_runs_paint: H %d, W %d exceed %d", H, W, KG_LABEL_MAX_SIDE);
     KG_TRY(kg_check_map_size("kg_runs_paint", H, W));
     KG_CHECK_ARG(out, "kg_runs_paint: null pointer (out)");
     KG_CHECK_ARG(runs || R == 0, "kg_runs_paint: null pointer (runs)");
     KG_CHECK_ARG(kg_aligned(runs, 3) && kg_aligned(out, 3), "kg_runs_paint: misaligned pointer");
-    KG_CHECK_ARG(!runs || kg_rl_apart(out, 4L * H * W, runs, 12L * R), "kg_runs_paint: out aliases runs");
+    KG_CHECK_ARG(!runs || kg_apart(out, 4L * H * W, runs, 12L * R), "kg_runs_paint: out aliases runs");
     long top = 0;
     if (R > 0) for (top = 1; top * 2 <= (long)R; top *= 2) {}
     hipLaunchKernelGGL(runs_paint_kernel, dim3(kg_grid_cap(((long)H * W + 255) / 256)), dim3(256), 0, (hipStream_t)stream, runs, (long)R, top, H, W,

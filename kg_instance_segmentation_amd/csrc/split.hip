@@ -29,7 +29,6 @@
 // atomics, no global scratch.
 #include "label_common.h"
 
-#define KG_SP_MAX_SIDE 32768            // H, W <= 2^15 as in measure.hip
 #define KG_SP_CELLS 16384               // the LDS budget: (h + 2) * (w + 2) cells of 16 bits, 32 KiB
 #define KG_SP_OPEN 0x3fff               // the rank field of a pixel of P that no seed has reached yet
 #define KG_SP_MAX_RANK 16382            // h * w <= 126 * 126 < KG_SP_MAX_RANK for every box that fits: no seed list of distinct pixels is cut
@@ -124,29 +123,21 @@ __global__ __launch_bounds__(256) void label_split_kernel(const int* __restrict_
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------
-static inline bool kg_sp_apart(const void* a, long abytes, const void* b, long bbytes) {
-    const char* pa = (const char*)a; const char* pb = (const char*)b;
-    return pa + abytes <= pb || pb + bbytes <= pa;
-}
-
 // labels, seeds: device int32 [nimg][H][W]; jobs: device int32 [m][8] = (img, id, y1, x1, y2, x2, nseeds, first_new), written by the
 // caller; out: device int32 [nimg][H][W]; rows: device int32 [m][4]
 extern "C" int kg_label_split(const int* labels, const int* seeds, int nimg, int H, int W, int connectivity, const int* jobs, int m, int* out,
                               int* rows, void* stream) {
     const char* fn = "kg_label_split";
-    KG_CHECK_ARG(nimg > 0 && H > 0 && W > 0 && m >= 0, "%s: bad size (nimg %d, H %d, W %d, m %d)", fn, nimg, H, W, m);
-    KG_CHECK_ARG(H <= KG_SP_MAX_SIDE && W <= KG_SP_MAX_SIDE, "%s: H %d, W %d exceed %d", fn, H, W, KG_SP_MAX_SIDE);
-    KG_TRY(kg_check_stack_size(fn, nimg, H, W));
+    KG_TRY(kg_check_job_stack(fn, labels, nimg, H, W, jobs, m));
     KG_CHECK_ARG(connectivity == 4 || connectivity == 8, "%s: connectivity %d (4 or 8)", fn, connectivity);
-    KG_CHECK_ARG(labels && seeds && out, "%s: null pointer (labels / seeds / out)", fn);
-    KG_CHECK_ARG((jobs && rows) || m == 0, "%s: null pointer (jobs / rows)", fn);
-    KG_CHECK_ARG(kg_aligned(labels, 3) && kg_aligned(seeds, 3) && kg_aligned(out, 3) && kg_aligned(jobs, 3) && kg_aligned(rows, 3),
-                 "%s: misaligned pointer", fn);
+    KG_CHECK_ARG(seeds && out, "%s: null pointer (seeds / out)", fn);
+    KG_CHECK_ARG(rows || m == 0, "%s: null pointer (rows)", fn);
+    KG_CHECK_ARG(kg_aligned(seeds, 3) && kg_aligned(out, 3) && kg_aligned(rows, 3), "%s: misaligned pointer", fn);
     const long lbytes = 4L * nimg * H * W;
-    KG_CHECK_ARG(kg_sp_apart(out, lbytes, labels, lbytes) && kg_sp_apart(out, lbytes, seeds, lbytes), "%s: out aliases labels / seeds", fn);
-    KG_CHECK_ARG(!rows || (kg_sp_apart(rows, 16L * m, labels, lbytes) && kg_sp_apart(rows, 16L * m, seeds, lbytes) &&
-                           kg_sp_apart(rows, 16L * m, out, lbytes)), "%s: rows aliases a map", fn);
-    KG_CHECK_ARG(!jobs || (kg_sp_apart(jobs, 32L * m, out, lbytes) && kg_sp_apart(jobs, 32L * m, rows, 16L * m)), "%s: jobs aliases out / rows", fn);
+    KG_CHECK_ARG(kg_apart(out, lbytes, labels, lbytes) && kg_apart(out, lbytes, seeds, lbytes), "%s: out aliases labels / seeds", fn);
+    KG_CHECK_ARG(!rows || (kg_apart(rows, 16L * m, labels, lbytes) && kg_apart(rows, 16L * m, seeds, lbytes) &&
+                           kg_apart(rows, 16L * m, out, lbytes)), "%s: rows aliases a map", fn);
+    KG_CHECK_ARG(!jobs || (kg_apart(jobs, 32L * m, out, lbytes) && kg_apart(jobs, 32L * m, rows, 16L * m)), "%s: jobs aliases out / rows", fn);
     hipStream_t s = (hipStream_t)stream;
     KG_HIP(hipMemcpyAsync(out, labels, (size_t)lbytes, hipMemcpyDeviceToDevice, s));
     if (m == 0) return KG_OK;

@@ -21,7 +21,6 @@
 // only subtracted and compared.
 #include "label_common.h"
 
-#define KG_TX_MAX_SIDE 32768            // as measure.hip: a box holds at most 2^30 pixels, so every count fits int32
 #define KG_TX_MAX_L 32
 #define KG_TX_CELLS (KG_TX_MAX_L * KG_TX_MAX_L)
 #define KG_TX_MAX_D 32
@@ -128,17 +127,11 @@ __global__ __launch_bounds__(256) void label_glcm_kernel(const int* __restrict__
 extern "C" int kg_label_glcm(const int* labels, int nimg, int H, int W, const void* image, int channels, int elem_bytes, const int* jobs, int m,
                              int levels, int* out, void* stream) {
     const char* fn = "kg_label_glcm";
-    KG_CHECK_ARG(nimg > 0 && H > 0 && W > 0 && m >= 0, "%s: bad size (nimg %d, H %d, W %d, m %d)", fn, nimg, H, W, m);
-    KG_CHECK_ARG(H <= KG_TX_MAX_SIDE && W <= KG_TX_MAX_SIDE, "%s: H %d, W %d exceed %d (the bound that keeps every count inside int32)", fn, H, W,
-                 KG_TX_MAX_SIDE);
-    KG_TRY(kg_check_stack_size(fn, nimg, H, W));
-    KG_CHECK_ARG(channels >= 1 && channels <= 4, "%s: channels %d (1 .. 4)", fn, channels);
-    KG_CHECK_ARG(elem_bytes == 1 || elem_bytes == 2, "%s: elem_bytes %d (1 or 2)", fn, elem_bytes);
+    KG_TRY(kg_check_job_stack(fn, labels, nimg, H, W, jobs, m));       // H, W <= KG_LABEL_MAX_SIDE: every count of a box fits int32
+    KG_TRY(kg_check_image(fn, image, channels, elem_bytes));
     KG_CHECK_ARG(levels >= 2 && levels <= KG_TX_MAX_L, "%s: levels %d (2 .. %d)", fn, levels, KG_TX_MAX_L);
-    KG_CHECK_ARG(labels && image, "%s: null pointer (labels / image)", fn);
-    KG_CHECK_ARG((jobs && out) || m == 0, "%s: null pointer (jobs / out)", fn);
-    KG_CHECK_ARG(kg_aligned(labels, 3) && kg_aligned(jobs, 3) && kg_aligned(out, 3) && kg_aligned(image, elem_bytes == 2 ? 1 : 0),
-                 "%s: misaligned pointer", fn);
+    KG_CHECK_ARG(out || m == 0, "%s: null pointer (out)", fn);
+    KG_CHECK_ARG(kg_aligned(out, 3), "%s: misaligned pointer", fn);
     if (m == 0) return KG_OK;
     hipStream_t s = (hipStream_t)stream;
     if (elem_bytes == 2)

@@ -26,8 +26,7 @@ import math
 
 import numpy as np
 
-from . import _lib, _labelmaps, labelmetrics
-from ._labelmaps import is_device
+from . import _lib, _labelmaps, components, labelmetrics, tiling
 
 KGLibraryError = _lib.KGLibraryError
 TILE_H, TILE_W = 32, 64                 # the tile of one workgroup (KG_DT_TH, KG_DT_TW of csrc/distance.hip): the tests need the seams
@@ -43,7 +42,7 @@ def _max_d2(fn, max_d2):
     return int(max_d2)
 
 
-def _square(fn, distance, least=1):
+def square(fn, distance, least=1):
     """floor(distance^2) of a float or an int distance; refused above 64 and where the square is below `least`"""
     if isinstance(distance, (bool, np.bool_)) or not isinstance(distance, (int, float, np.integer, np.floating)) or not math.isfinite(distance) \
             or distance < 0:
@@ -60,7 +59,7 @@ def _ring(fn, inner, outer):
     if not (isinstance(inner, (int, float, np.integer, np.floating)) and isinstance(outer, (int, float, np.integer, np.floating))) \
             or not 0 <= inner < outer:
         raise KGLibraryError(f"{fn}: need 0 <= inner < outer (inner {inner!r}, outer {outer!r})")
-    return _square(fn, inner, 0), _square(fn, outer)
+    return square(fn, inner, 0), square(fn, outer)
 
 
 def _want(fn, want):
@@ -128,7 +127,7 @@ def expand_labels_host(labels, distance):
     """Every background (0) pixel within `distance` of a non-zero pixel takes the value of the nearest one; everything else is kept.  This is
     skimage.segmentation.expand_labels with THIS project's tie rule: among equally near values the smallest (signed) wins, whatever the
     order of the pixels -- skimage takes whichever scipy's distance transform happened to index."""
-    return _regrow_host("expand_labels_host", labels, EXPAND, 0, _square("expand_labels_host", distance))
+    return _regrow_host("expand_labels_host", labels, EXPAND, 0, square("expand_labels_host", distance))
 
 
 def ring_labels_host(labels, inner, outer):
@@ -139,7 +138,7 @@ def ring_labels_host(labels, inner, outer):
 
 def shrink_labels_host(labels, distance, frame=False):
     """A non-zero pixel survives iff it lies farther than `distance` from every pixel with another value (and from the frame, if asked)."""
-    return _regrow_host("shrink_labels_host", labels, SHRINK, 0, _square("shrink_labels_host", distance), bool(frame))
+    return _regrow_host("shrink_labels_host", labels, SHRINK, 0, square("shrink_labels_host", distance), bool(frame))
 
 
 def _result(rows, max_d2):
@@ -150,30 +149,6 @@ def _result(rows, max_d2):
     out["radius"] = np.sqrt(rows[:, 0].astype(np.float64))
     out["saturated"] = rows[:, 0] > max_d2
     return out
-
-
-def _job_table(fn, maps, n, jobs, stats, stats_of):
-    """measure.measure's n / jobs / stats arguments -> int64 [m, 6] jobs, clamped to the map"""
-    from . import measure
-    nimg, H, W = maps.shape
-    if jobs is not None:
-        if n is not None or stats is not None:
-            raise KGLibraryError(f"{fn}: jobs cannot be given together with n / stats")
-        j = measure._host_jobs(fn, jobs)
-    else:
-        if n is None:
-            raise KGLibraryError(f"{fn}: the instance count n or a job table is needed")
-        ns = measure._counts(fn, n, nimg)
-        if stats is None:
-            per = [stats_of(maps[i], ns[i]) for i in range(nimg)]
-        else:
-            per = [stats] if nimg == 1 and np.ndim(stats) == 2 else list(stats)
-            if len(per) != nimg or any(len(np.asarray(s)) != k for s, k in zip(per, ns)):
-                raise KGLibraryError(f"{fn}: stats must be [n, 5] per label map ({nimg} map(s), counts {ns})")
-        j = np.concatenate([measure.jobs_from_stats(s, i) for i, s in enumerate(per)]).astype(np.int64).reshape(-1, 6)
-    j = j.copy()
-    j[:, 2:4] = np.clip(j[:, 2:4], 0, [H, W]); j[:, 4:6] = np.clip(j[:, 4:6], 0, [H, W])
-    return j
 
 
 def inscribed_rows_host(labels, d2, jobs):
@@ -206,7 +181,7 @@ def inscribed_host(labels, n=None, jobs=None, stats=None, max_d2=MAX_D2, frame=T
       saturated  d2max > max_d2: the object is thicker than the search radius, and radius is only a lower bound
     n / jobs / stats: what is measured, as measure.measure_host / measure.measure take them."""
     d2, _, maps, _ = _transform_host("inscribed_host", labels, max_d2, frame)
-    j = _job_table("inscribed_host", maps, n, jobs, stats, labelmetrics.label_stats_host)
+    j = _labelmaps.job_table("inscribed_host", maps, n, jobs, stats, labelmetrics.label_stats_host)
     return _result(inscribed_rows_host(maps, d2, j), int(max_d2))
 
 
@@ -233,9 +208,8 @@ def combine_bands(rows, owner, n_jobs, W):
 # ---- device -----------------------------------------------------------------------------------------------------------------------------
 
 def _stack(fn, labels):
-    """-> (device int32 [nimg, H, W], the caller's shape)"""
-    t = _labelmaps.device_maps(fn, labels, True)
-    return t.view((-1,) + t.shape[-2:]), t.shape
+    """-> (device int32 [nimg, H, W], the caller's shape); the transform has no side bound"""
+    return _labelmaps.device_stack(fn, labels, bound=False)
 
 
 def distance(labels, max_d2, frame=False, want=("d2", "nearest")):
@@ -268,7 +242,7 @@ def _regrow(fn, labels, op, lo2, hi2, frame=False):
 def expand_labels(labels, distance):
     """expand_labels_host on the device (skimage.segmentation.expand_labels with this project's tie rule: among equally near values the
     smallest wins): device int32 [H, W] or [nimg, H, W] -> a new device int32 map.  One launch; d2 and nearest never reach memory."""
-    return _regrow("expand_labels", labels, EXPAND, 0, _square("expand_labels", distance))
+    return _regrow("expand_labels", labels, EXPAND, 0, square("expand_labels", distance))
 
 
 def ring_labels(labels, inner, outer):
@@ -279,7 +253,7 @@ def ring_labels(labels, inner, outer):
 
 def shrink_labels(labels, distance, frame=False):
     """shrink_labels_host on the device.  One launch."""
-    return _regrow("shrink_labels", labels, SHRINK, 0, _square("shrink_labels", distance), frame)
+    return _regrow("shrink_labels", labels, SHRINK, 0, square("shrink_labels", distance), frame)
 
 
 def inscribed_rows(labels, d2, jobs):
@@ -288,8 +262,7 @@ def inscribed_rows(labels, d2, jobs):
     import torch
     from ._lib import ptr, stream_ptr
     lab, _ = _stack("inscribed", labels)
-    dd = _labelmaps.device_maps("inscribed", d2, True)
-    dd = dd.view((-1,) + dd.shape[-2:])
+    dd, _ = _stack("inscribed", d2)
     if dd.shape != lab.shape or dd.device != lab.device:
         raise KGLibraryError(f"inscribed: d2 of {tuple(dd.shape)} for label maps of {tuple(lab.shape)}: one shape and one device")
     nimg, H, W = lab.shape
@@ -308,7 +281,7 @@ def inscribed(labels, n=None, jobs=None, stats=None, max_d2=MAX_D2, frame=True, 
     only), one kg_label_inscribed launch, one upload (the jobs) and one device -> host copy (the rows)."""
     max_d2 = _max_d2("inscribed", max_d2)
     lab, _ = _stack("inscribed", labels)
-    j = _job_table("inscribed", lab, n, jobs, stats, labelmetrics.label_stats)
+    j = _labelmaps.job_table("inscribed", lab, n, jobs, stats, labelmetrics.label_stats)
     pieces, owner = labelmetrics.split_jobs(j, max_job_pixels)
     d2, _ = distance(lab, max_d2, frame, want=("d2",))
     rows = inscribed_rows(lab, d2, pieces).cpu().numpy()
@@ -336,14 +309,6 @@ def _grown_table(old, rows, new_rows):
     return out
 
 
-def _check_instances(fn, inst):
-    from .instances import Instances
-    if not isinstance(inst, Instances):
-        raise KGLibraryError(f"{fn}: an Instances or a TiledInstances")
-    if np.asarray(inst.table).shape != (len(inst), 8):
-        raise KGLibraryError(f"{fn}: a table of {np.asarray(inst.table).shape} for {len(inst)} instances")
-
-
 def expand_instances(inst, distance):
     """expand_labels for an Instances / TiledInstances: a new object of the same type with labels replaced and the table refreshed
     (tiling.table_from_labels over the old boxes grown by ceil(distance) and clamped); area_full, dets and masks are kept, so the ids still
@@ -355,31 +320,18 @@ def expand_instances_batch(insts, distance):
     """expand_instances for predict_instances' list (entries may be None): ONE kg_label_regrow launch for all images of one output size,
     one kg_label_table launch per image and one device -> host copy of the tables per size."""
     import torch
-    from . import tiling
-    from .components import _like
-    from .inference import size_groups
-    _square("expand_instances", distance)
+    square("expand_instances", distance)
     out = list(insts)
-    todo = [i for i, v in enumerate(insts) if v is not None]
-    for i in todo:
-        _check_instances("expand_instances", insts[i])
-    host = [i for i in todo if not is_device(insts[i].labels)]
-    for i in host:
-        lab = insts[i].labels.numpy() if torch.is_tensor(insts[i].labels) else np.asarray(insts[i].labels)
+
+    def host_one(i, inst, lab):
         new = expand_labels_host(lab, distance)
-        jobs, rows = _grown_jobs(insts[i].table, distance, *lab.shape)
-        out[i] = _like(insts[i], new, _grown_table(insts[i].table, rows, tiling.table_from_labels_host(new, jobs)))
-    todo = [i for i in todo if i not in host]
-    for (H, W), members in size_groups([tuple(insts[i].labels.shape) for i in todo]):
-        idx = [todo[k] for k in members]
-        stack = insts[idx[0]].labels[None] if len(idx) == 1 else torch.stack([insts[i].labels for i in idx])
+        jobs, rows = _grown_jobs(inst.table, distance, *lab.shape)
+        out[i] = components.like(inst, new, _grown_table(inst.table, rows, tiling.table_from_labels_host(new, jobs)))
+    for idx, stack, H, W in _labelmaps.size_batches("expand_instances", insts, host_one):
         new = expand_labels(stack, distance)
         jr = [_grown_jobs(insts[i].table, distance, H, W) for i in idx]
         tabs = [tiling.table_from_labels(new[k], jr[k][0]) for k in range(len(idx))]
         got = (torch.cat(tabs) if len(tabs) > 1 else tabs[0]).cpu().numpy()
-        r = 0
-        for k, i in enumerate(idx):
-            rows = jr[k][1]
-            out[i] = _like(insts[i], new[k], _grown_table(insts[i].table, rows, got[r:r + len(rows)]))
-            r += len(rows)
+        for k, (i, a, b) in enumerate(_labelmaps.deal(insts, idx, [len(r[1]) for r in jr])):
+            out[i] = components.like(insts[i], new[k], _grown_table(insts[i].table, jr[k][1], got[a:b]))
     return out

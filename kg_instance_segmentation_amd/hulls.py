@@ -41,21 +41,12 @@ Semantics (include/kgnet_hip.h is the normative text)
 import numpy as np
 
 from . import _lib, _labelmaps, labelmetrics
-from ._labelmaps import is_device
+from ._labelmaps import JOB_COLUMNS as _JOB_COLUMNS, MAX_SIDE, device_stack, host_stack, out_tensor  # noqa: F401  (MAX_SIDE: public here)
 
 KGLibraryError = _lib.KGLibraryError
-MAX_SIDE = 32768
 MAX_ROWS = 4095                                                        # rows of a box the device takes: 4096 lattice lines in LDS
 ROW_COLUMNS = ("area", "count", "area2", "feret_max2", "fmax_i", "fmax_j", "minw_num", "minw_den2", "minw_edge", "status")
-_JOB_COLUMNS = "(img, id, y1, x1, y2, x2)"
 _ROW_JOB_COLUMNS = "(img, id, y1, x1, y2, x2, vert_at, cap)"
-
-
-def _side(fn, maps):
-    H, W = maps.shape[-2:]
-    if H > MAX_SIDE or W > MAX_SIDE:
-        raise KGLibraryError(f"{fn}: a map of {H} x {W} exceeds {MAX_SIDE}")
-    return maps
 
 
 class Hulls:
@@ -268,24 +259,13 @@ def extent_ring(me, y1=0, x1=0):
     return np.array(left[:1] + right + left[:0:-1], np.int64)
 
 
-def _maps(fn, labels):
-    return _side(fn, _labelmaps.host_maps(fn, labels, True)[0])
-
-
-def _host_job_table(fn, maps, jobs_or_n):
-    from .distance import _job_table
-    if np.ndim(jobs_or_n) == 2 or (np.ndim(jobs_or_n) == 1 and np.size(jobs_or_n) == 0):        # an empty list is no jobs
-        return _job_table(fn, maps, None, jobs_or_n if np.size(jobs_or_n) else np.zeros((0, 6), np.int64), None, None)
-    return _job_table(fn, maps, jobs_or_n, None, None, labelmetrics.label_stats_host)
-
-
 def hulls_host(labels, jobs_or_n):
     """labels: integers [H, W] or [nimg, H, W]; jobs_or_n: jobs [m, 6] = (img, id, y1, x1, y2, x2), or the instance count n (one per map
     for a stack): the ids 1 .. n inside their own boxes (labelmetrics.label_stats_host) -> Hulls, one row per job.  The ring is the
     monotone chain over the corners C(P) themselves, not the extent form.  Never size-limited."""
-    maps = _maps("hulls_host", labels)
+    maps = host_stack("hulls_host", labels)
     nimg, H, W = maps.shape
-    j = _host_job_table("hulls_host", maps, jobs_or_n)
+    j = _labelmaps.host_job_table("hulls_host", maps, jobs_or_n, labelmetrics.label_stats_host)
     return _assemble([_job_hull(maps[i], H, W, rest) if 0 <= i < nimg else _NONE for i, *rest in j.tolist()])
 
 
@@ -336,17 +316,6 @@ def merge_bands(pieces, owner, m):
 
 # ---- device -----------------------------------------------------------------------------------------------------------------------------
 
-def _device_maps(fn, t):
-    t = _labelmaps.device_maps(fn, t, True)
-    return _side(fn, t.view((-1,) + t.shape[-2:]))
-
-
-def _out(fn, what, t, shape, dtype, dev):
-    if not is_device(t) or t.dtype != dtype or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
-        raise KGLibraryError(f"{fn}: {what} must be a contiguous {str(dtype).replace('torch.', '')} {list(shape)} tensor on the maps' device")
-    return t
-
-
 def hull_rows(labels, jobs, V, rows=None, verts=None):
     """kg_label_hulls as it is: labels device int32 [H, W] or [nimg, H, W]; jobs host integers [m, 8] = (img, id, y1, x1, y2, x2, vert_at,
     cap) (uploaded once) or a device int32 tensor -> (rows device int64 [m, 10] = ROW_COLUMNS, verts device int32 [V, 2] = (y, x)).
@@ -354,15 +323,15 @@ def hull_rows(labels, jobs, V, rows=None, verts=None):
     vertex slots the table names change.  One launch, no copy back, no synchronisation."""
     import torch
     from ._lib import ptr, stream_ptr
-    lab = _device_maps("hull_rows", labels)
+    lab = device_stack("hull_rows", labels)[0]
     nimg, H, W = lab.shape
     jd = _labelmaps.device_jobs("hull_rows", jobs, 8, _ROW_JOB_COLUMNS, lab.device)
     m = jd.shape[0]
     V = int(V)
     if not 0 <= V <= 2 ** 31 - 1:
         raise KGLibraryError(f"hull_rows: V {V}")
-    rows = torch.zeros(m, 10, dtype=torch.int64, device=lab.device) if rows is None else _out("hull_rows", "rows", rows, (m, 10), torch.int64, lab.device)
-    verts = torch.zeros(V, 2, dtype=torch.int32, device=lab.device) if verts is None else _out("hull_rows", "verts", verts, (V, 2), torch.int32, lab.device)
+    rows = torch.zeros(m, 10, dtype=torch.int64, device=lab.device) if rows is None else out_tensor("hull_rows", "rows", rows, (m, 10), torch.int64, lab.device)
+    verts = torch.zeros(V, 2, dtype=torch.int32, device=lab.device) if verts is None else out_tensor("hull_rows", "verts", verts, (V, 2), torch.int32, lab.device)
     with torch.cuda.device(lab.device):
         _lib.call("kg_label_hulls", ptr(lab), nimg, H, W, ptr(jd) if m else None, m, ptr(rows) if m else None, ptr(verts) if V else None, V,
                   stream_ptr())
@@ -405,36 +374,22 @@ def hulls(labels, n=None, jobs=None, stats=None, max_job_pixels=65536):
     The jobs are cut into pieces (band_jobs), every piece gets a slab of 2 * (h + 1) vertices; one upload, ONE kg_label_hulls launch, one
     copy back of rows and slabs in one buffer; the host compacts the slabs and merges the pieces of a job (merge_bands).  No job is
     traced on the host."""
-    from .distance import _job_table
-    lab = _device_maps("hulls", labels)
-    return _device_hulls(lab, _job_table("hulls", lab, n, jobs, stats, labelmetrics.label_stats), max_job_pixels)
+    lab = device_stack("hulls", labels)[0]
+    return _device_hulls(lab, _labelmaps.job_table("hulls", lab, n, jobs, stats, labelmetrics.label_stats), max_job_pixels)
 
 
 # ---- Instances ----------------------------------------------------------------------------------------------------------------------------
 
 def _instance_hulls(insts, max_job_pixels=65536):
     """-> one Hulls per entry (None for a None entry); the entries themselves are not touched"""
-    import torch
-    from . import distance
-    from .inference import size_groups
     out = [None] * len(insts)
-    todo = [i for i, v in enumerate(insts) if v is not None]
-    for i in todo:
-        distance._check_instances("hulls_instances", insts[i])
-    host = [i for i in todo if not is_device(insts[i].labels)]
-    for i in host:
-        lab = insts[i].labels.numpy() if torch.is_tensor(insts[i].labels) else np.asarray(insts[i].labels)
-        out[i] = hulls_host(lab, _labelmaps.instance_jobs(insts[i], 0, 0, *lab.shape))
-    todo = [i for i in todo if i not in host]
-    for (H, W), members in size_groups([tuple(insts[i].labels.shape) for i in todo]):
-        idx = [todo[k] for k in members]
-        stack = insts[idx[0]].labels[None] if len(idx) == 1 else torch.stack([insts[i].labels for i in idx])
-        got = _device_hulls(_device_maps("hulls_instances", stack),
-                            np.concatenate([_labelmaps.instance_jobs(insts[i], k, 0, H, W) for k, i in enumerate(idx)]), max_job_pixels)
-        r = 0
-        for i in idx:
-            out[i] = got.slice(r, r + len(insts[i]))
-            r += len(insts[i])
+
+    def host_one(i, inst, lab):
+        out[i] = hulls_host(lab, _labelmaps.instance_jobs(inst, 0, 0, *lab.shape))
+    for idx, stack, H, W in _labelmaps.size_batches("hulls_instances", insts, host_one):
+        got = _device_hulls(device_stack("hulls_instances", stack)[0], _labelmaps.batch_jobs(insts, idx, 0, H, W), max_job_pixels)
+        for i, a, b in _labelmaps.deal(insts, idx):
+            out[i] = got.slice(a, b)
     return out
 
 

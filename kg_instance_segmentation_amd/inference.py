@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib, postprocessing
+from ._labelmaps import size_groups  # (its owner is the label-map batch walk; it stays importable here)
 
 
 def image_row_ranges(img, nimg):
@@ -18,14 +19,6 @@ def image_row_ranges(img, nimg):
         raise _lib.KGLibraryError("image_row_ranges: rows are not sorted by image")
     starts = np.searchsorted(img, np.arange(nimg + 1), side="left")
     return [(int(starts[i]), int(starts[i + 1])) for i in range(nimg)]
-
-
-def size_groups(image_sizes):
-    """Images grouped by output size, in order of first appearance: [((h, w), [image indices])]."""
-    groups = {}
-    for i, hw in enumerate(image_sizes):
-        groups.setdefault((int(hw[0]), int(hw[1])), []).append(i)
-    return list(groups.items())
 
 
 def predict(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None, device_u8=False, max_workspace_bytes=None, packed=False):

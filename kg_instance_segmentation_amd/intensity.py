@@ -41,15 +41,14 @@ from fractions import Fraction
 
 import numpy as np
 
-from . import _lib, _labelmaps, labelmetrics, measure
-from ._labelmaps import is_device
+from . import _lib, _labelmaps, labelmetrics
+from ._labelmaps import JOB_COLUMNS as _JOB_COLUMNS, MAX_CHANNELS, check_cap, device_args, host_args, is_device, job_rows, job_table
 from .labelmetrics import split_jobs
 
 KGLibraryError = _lib.KGLibraryError
 MAX_Q = 8
 MAX_DEN = 1_000_000
 DEFAULT_Q = (Fraction(1, 20), Fraction(1, 4), Fraction(1, 2), Fraction(3, 4), Fraction(19, 20))
-_JOB_COLUMNS = "(img, id, y1, x1, y2, x2)"
 _HIST_JOB_COLUMNS = "(img, id, y1, x1, y2, x2, channel, shift, prefix)"
 
 
@@ -114,7 +113,7 @@ class Quantiles:
     def __init__(self, raw, q=None):
         self.q = as_fractions(q)
         r = np.ascontiguousarray(raw, np.int64)
-        if r.ndim != 3 or not 1 <= r.shape[1] <= measure.MAX_CHANNELS or r.shape[2] != 1 + 2 * len(self.q):
+        if r.ndim != 3 or not 1 <= r.shape[1] <= MAX_CHANNELS or r.shape[2] != 1 + 2 * len(self.q):
             raise KGLibraryError(f"Quantiles: raw must be integers [n, C, 1 + 2 Q] with Q = {len(self.q)}, not {r.shape}")
         self.raw = r
 
@@ -233,14 +232,6 @@ class Histograms:
 
 # ---- host statement of the semantics ----------------------------------------------------------------------------------------------------
 
-def _host_args(fn, labels, image):
-    maps = measure._side(fn, _labelmaps.host_maps(fn, labels, True)[0])
-    img = measure._host_image(fn, image, maps.shape)
-    if img is None:
-        raise KGLibraryError(f"{fn}: an image is needed")
-    return maps, img
-
-
 def _pixels(maps, img, job):
     """the values [|P|, C] of one job (img, id, y1, x1, y2, x2), or None for a bad job"""
     nimg, H, W = maps.shape
@@ -256,13 +247,9 @@ def quantiles_host(labels, jobs_or_n, image, q=None):
     """labels: integers [H, W] or [nimg, H, W]; jobs_or_n: jobs [m, 6] = (img, id, y1, x1, y2, x2), or the instance count n (one per map
     for a stack): the ids 1 .. n inside their own boxes (labelmetrics.label_stats_host); image: uint8 / uint16 [H, W, C] /
     [nimg, H, W, C]; q: as_fractions' -> int64 [m, C, 1 + 2 Q].  Per job and channel: sort, index by the integer rule.  Nothing split."""
-    from .distance import _job_table
-    maps, img = _host_args("quantiles_host", labels, image)
+    maps, img = host_args("quantiles_host", labels, image)
     qs = as_fractions(q)
-    if np.ndim(jobs_or_n) == 2:
-        j = _job_table("quantiles_host", maps, None, jobs_or_n, None, None)
-    else:
-        j = _job_table("quantiles_host", maps, jobs_or_n, None, None, labelmetrics.label_stats_host)
+    j = _labelmaps.host_job_table("quantiles_host", maps, jobs_or_n, labelmetrics.label_stats_host)
     C = img.shape[3]
     out = np.zeros((len(j), C, 1 + 2 * len(qs)), np.int64)
     for a, job in enumerate(j.tolist()):
@@ -278,7 +265,7 @@ def quantiles_host(labels, jobs_or_n, image, q=None):
 
 def histograms_host(labels, jobs, image):
     """labels, image as quantiles_host; jobs: integers [m, 9] = (img, id, y1, x1, y2, x2, channel, shift, prefix) -> int64 [m, 256]"""
-    maps, img = _host_args("histograms_host", labels, image)
+    maps, img = host_args("histograms_host", labels, image)
     j = _labelmaps.host_jobs("histograms_host", jobs, 9, _HIST_JOB_COLUMNS).astype(np.int64)
     C = img.shape[3]
     out = np.zeros((len(j), 256), np.int64)
@@ -347,25 +334,6 @@ def quantiles_from_histograms(jobs, C, wide, q, max_job_pixels, hist_rows):
 
 # ---- device -----------------------------------------------------------------------------------------------------------------------------
 
-def _device_args(fn, labels, image):
-    lab = measure._device_maps(fn, labels)
-    if image is None:
-        raise KGLibraryError(f"{fn}: an image is needed")
-    return lab, measure._device_image(fn, image, lab.shape, lab.device)
-
-
-def _rows(entry, lab, img, jd, extra, shape):
-    import torch
-    from ._lib import ptr, stream_ptr
-    nimg, H, W = lab.shape
-    m = jd.shape[0]
-    out = torch.empty((m,) + shape, dtype=torch.int32, device=lab.device)
-    with torch.cuda.device(lab.device):
-        _lib.call(entry, ptr(lab), nimg, H, W, ptr(img), img.shape[3], img.element_size(), ptr(jd) if m else None, m, *extra,
-                  ptr(out) if m else None, stream_ptr())
-    return out
-
-
 def quantile_rows(labels, jobs, image, q=None):
     """kg_label_quantiles as it is: labels device int32 [H, W] or [nimg, H, W]; jobs host integers [m, 6] (uploaded once) or a device int32
     tensor; image a host array (uploaded once) or a device tensor; q: as_fractions' (the table is uploaded), or a device int32 [Q, 2]
@@ -373,7 +341,7 @@ def quantile_rows(labels, jobs, image, q=None):
     split."""
     import torch
     from . import ops
-    lab, img = _device_args("quantile_rows", labels, image)
+    lab, img = device_args("quantile_rows", labels, image)
     if torch.is_tensor(q):
         if q.dtype != torch.int32 or q.dim() != 2 or q.shape[1] != 2 or not 1 <= q.shape[0] <= MAX_Q or q.device != lab.device:
             raise KGLibraryError(f"quantile_rows: a device quantile table must be int32 [Q, 2], 1 <= Q <= {MAX_Q}, on the maps' device")
@@ -382,27 +350,21 @@ def quantile_rows(labels, jobs, image, q=None):
         qd = ops.h2d(q_table(q), lab.device)
     jd = _labelmaps.device_jobs("quantile_rows", jobs, 6, _JOB_COLUMNS, lab.device)
     Q = qd.shape[0]
-    return _rows("kg_label_quantiles", lab, img, jd, (_lib.ptr(qd), Q), (img.shape[3], 1 + 2 * Q))
+    return job_rows("kg_label_quantiles", lab, img, jd, (_lib.ptr(qd), Q), (img.shape[3], 1 + 2 * Q))
 
 
 def histogram_rows(labels, jobs, image):
     """kg_label_histograms as it is: labels, image as quantile_rows; jobs host integers [m, 9] = (img, id, y1, x1, y2, x2, channel, shift,
     prefix) (uploaded once) or a device int32 tensor -> device int32 [m, 256].  One launch, no copy back, no synchronisation."""
-    lab, img = _device_args("histogram_rows", labels, image)
+    lab, img = device_args("histogram_rows", labels, image)
     jd = _labelmaps.device_jobs("histogram_rows", jobs, 9, _HIST_JOB_COLUMNS, lab.device)
-    return _rows("kg_label_histograms", lab, img, jd, (), (256,))
-
-
-def _check_cap(fn, max_job_pixels):
-    if int(max_job_pixels) < 1:
-        raise KGLibraryError(f"{fn}: max_job_pixels {max_job_pixels}")
-    return int(max_job_pixels)
+    return job_rows("kg_label_histograms", lab, img, jd, (), (256,))
 
 
 def _device_quantiles(lab, img, j, qs, max_job_pixels):
     """lab, img: device tensors; j: clamped host jobs [m, 6] -> Quantiles"""
     from . import ops
-    cap = _check_cap("quantiles", max_job_pixels)
+    cap = check_cap("quantiles", max_job_pixels)
     C, Q = img.shape[3], len(qs)
     raw = np.zeros((len(j), C, 1 + 2 * Q), np.int64)
     large = (j[:, 4] - j[:, 2]) * (j[:, 5] - j[:, 3]) > cap
@@ -424,9 +386,8 @@ def quantiles(labels, n=None, jobs=None, image=None, q=None, stats=None, max_job
     image: a host uint8 / uint16 array [H, W, C] / [nimg, H, W, C] (uploaded once) or a device tensor; q: as_fractions'.
     ONE kg_label_quantiles launch, one upload (the quantile table and the jobs) and one copy back when no job holds more than
     max_job_pixels pixels; such jobs take the histogram route (one more launch and copy back, two for uint16)."""
-    from .distance import _job_table
-    lab, img = _device_args("quantiles", labels, image)
-    return _device_quantiles(lab, img, _job_table("quantiles", lab, n, jobs, stats, labelmetrics.label_stats), as_fractions(q), max_job_pixels)
+    lab, img = device_args("quantiles", labels, image)
+    return _device_quantiles(lab, img, job_table("quantiles", lab, n, jobs, stats, labelmetrics.label_stats), as_fractions(q), max_job_pixels)
 
 
 def histograms(labels, n=None, jobs=None, image=None, shift=None, stats=None, max_job_pixels=65536):
@@ -434,14 +395,13 @@ def histograms(labels, n=None, jobs=None, image=None, shift=None, stats=None, ma
     [m, C, 256]).  labels, n / jobs / stats, image as quantiles; shift: None (0 for uint8, 8 for uint16) or 0 .. 8.  A job of more than
     max_job_pixels pixels is cut into pieces (labelmetrics.split_jobs) whose rows are added on the host.  ONE kg_label_histograms launch,
     one upload and one copy back."""
-    from .distance import _job_table
-    lab, img = _device_args("histograms", labels, image)
-    j = _job_table("histograms", lab, n, jobs, stats, labelmetrics.label_stats)
+    lab, img = device_args("histograms", labels, image)
+    j = job_table("histograms", lab, n, jobs, stats, labelmetrics.label_stats)
     shift = (8 if img.element_size() == 2 else 0) if shift is None else int(shift)
     if not 0 <= shift <= 8:
         raise KGLibraryError(f"histograms: shift {shift} (0 .. 8)")
     C = img.shape[3]
-    pieces, owner = split_jobs(j, _check_cap("histograms", max_job_pixels))
+    pieces, owner = split_jobs(j, check_cap("histograms", max_job_pixels))
     rows = histogram_rows(lab, _hist_jobs(np.repeat(pieces, C, 0), np.tile(np.arange(C), len(pieces)), shift, -1), img).cpu().numpy()
     counts = np.zeros((len(j), C, 256), np.int64)
     np.add.at(counts, owner, rows.reshape(len(pieces), C, 256).astype(np.int64))
@@ -450,50 +410,27 @@ def histograms(labels, n=None, jobs=None, image=None, shift=None, stats=None, ma
 
 # ---- Instances ----------------------------------------------------------------------------------------------------------------------------
 
-def _instance_stats(fn, inst):
-    from .instances import Instances
-    if not isinstance(inst, Instances):
-        raise KGLibraryError(f"{fn}: an Instances or a TiledInstances")
-    stats = np.asarray(inst.table, np.int64).reshape(-1, 8)[:, 1:6]
-    if len(stats) != len(inst):
-        raise KGLibraryError(f"{fn}: a table of {len(stats)} rows for {len(inst)} instances")
-    return stats
-
-
 def quantiles_instances(inst, image, q=None, max_job_pixels=65536):
     """quantiles for an Instances / TiledInstances -> Quantiles with len(inst) rows: ids 1 .. n, boxes from table[:, 2:6]; an instance with
     no visible pixel gets zeros (NaN once derived).  image: uint8 / uint16 [H, W, C] at the label map's size (host array or device
     tensor).  A host label map (assemble_host's result) goes through quantiles_host."""
-    import torch
-    stats = _instance_stats("quantiles_instances", inst)
+    stats = _labelmaps.instance_stats("quantiles_instances", inst)
     if is_device(inst.labels):
         return quantiles(inst.labels, len(inst), image=image, q=q, stats=stats, max_job_pixels=max_job_pixels)
-    lab = inst.labels.numpy() if torch.is_tensor(inst.labels) else inst.labels
-    if torch.is_tensor(image):
-        image = image.cpu().numpy()
-        image = image.view(np.uint16) if image.dtype == np.int16 else image
     qs = as_fractions(q)
-    return Quantiles(quantiles_host(lab, measure.jobs_from_stats(stats), image, qs), qs)
+    return Quantiles(quantiles_host(_labelmaps.host_labels(inst), _labelmaps.jobs_from_stats(stats), _labelmaps.host_pixels(image), qs), qs)
 
 
 def quantiles_instances_batch(insts, images, q=None, max_job_pixels=65536):
     """quantiles_instances for predict_instances' list (entries may be None), in place: every entry's `quantiles` is set.  ONE launch for
     all images of one output size.  images: uint8 / uint16 [N, h, w, C] (host array or device tensor), one image per entry, at the label
     maps' size."""
-    import torch
-    from .inference import size_groups
     qs = as_fractions(q)
     if images is None or len(images) != len(insts):
         raise KGLibraryError(f"quantiles: {0 if images is None else len(images)} images for {len(insts)} entries")
-    todo = [i for i, v in enumerate(insts) if v is not None]
-    for _, members in size_groups([tuple(insts[i].labels.shape) for i in todo]):
-        idx = [todo[k] for k in members]
-        stack = torch.stack([insts[i].labels for i in idx])
-        ns = [len(insts[i]) for i in idx]
-        got = quantiles(stack, ns, image=images[idx] if len(idx) != len(insts) else images, q=qs,
-                        stats=[_instance_stats("quantiles_instances_batch", insts[i]) for i in idx], max_job_pixels=max_job_pixels)
-        r = 0
-        for i, k in zip(idx, ns):
-            insts[i].quantiles = Quantiles(got.raw[r:r + k], qs)
-            r += k
+    for idx, stack, _, _ in _labelmaps.size_batches("quantiles_instances_batch", insts):
+        got = quantiles(stack, [len(insts[i]) for i in idx], image=images[idx] if len(idx) != len(insts) else images, q=qs,
+                        stats=[_labelmaps.instance_stats("quantiles_instances_batch", insts[i]) for i in idx], max_job_pixels=max_job_pixels)
+        for i, a, b in _labelmaps.deal(insts, idx):
+            insts[i].quantiles = Quantiles(got.raw[a:b], qs)
     return insts

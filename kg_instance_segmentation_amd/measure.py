@@ -34,14 +34,12 @@ import math
 import numpy as np
 
 from . import _lib, _labelmaps, labelmetrics
-from ._labelmaps import is_device
+from ._labelmaps import JOB_COLUMNS, MAX_CHANNELS, MAX_SIDE, SUMS_FIT, is_device, jobs_from_stats  # noqa: F401  (MAX_SIDE, jobs_from_stats: public here)
 from .labelmetrics import split_jobs  # noqa: F401  (the band rule is labelmetrics': columns 0 and 1 of a job pass through it untouched)
 
 KGLibraryError = _lib.KGLibraryError
 GEOMETRY_COLUMNS = ("area", "sum_y", "sum_x", "sum_yy", "sum_yx", "sum_xx", "edges", "edges_border", "edges_contact", "boundary_pixels")
 CHANNEL_COLUMNS = ("sum", "sumsq", "min", "max")
-MAX_SIDE = 32768
-MAX_CHANNELS = 4
 
 
 def columns(C):
@@ -139,67 +137,15 @@ class Measurements:
 
 # ---- host statement of the semantics ----------------------------------------------------------------------------------------------------
 
-def _side(fn, maps):
-    """[nimg, H, W] maps (host or device) as they came, once their sides are known to fit"""
-    H, W = maps.shape[-2:]
-    if H > MAX_SIDE or W > MAX_SIDE:
-        raise KGLibraryError(f"{fn}: a map of {H} x {W} exceeds {MAX_SIDE} (the bound that keeps every sum inside int64)")
-    return maps
-
-
-def _host_image(fn, image, shape):
-    """-> [nimg, H, W, C] or None"""
-    if image is None:
-        return None
-    a = np.asarray(image)
-    if a.dtype not in (np.uint8, np.uint16):
-        raise KGLibraryError(f"{fn}: the image must be uint8 or uint16, not {a.dtype}")
-    if a.ndim == 3 and shape[0] == 1:
-        a = a[None]
-    if a.ndim != 4 or a.shape[:3] != tuple(shape) or not 1 <= a.shape[3] <= MAX_CHANNELS:
-        raise KGLibraryError(f"{fn}: an image of {a.shape} for label maps of {tuple(shape)}: [nimg, H, W, C] with 1 <= C <= {MAX_CHANNELS}")
-    return a
-
-
-_JOB_COLUMNS = "(img, id, y1, x1, y2, x2)"
-
-
-def _host_jobs(fn, jobs):
-    return _labelmaps.host_jobs(fn, jobs, 6, _JOB_COLUMNS).astype(np.int64)
-
-
-def jobs_from_stats(stats, img=0):
-    """stats: integers [n, 5] = (area, y1, x1, y2, x2) of the ids 1 .. n of image `img` (labelmetrics.STATS_COLUMNS; columns 1:6 of an
-    Instances table) -> int32 [n, 6] jobs.  An id with area 0 gets an empty box, hence a row of zeros."""
-    s = np.asarray(stats)
-    if s.ndim != 2 or s.shape[1] != 5 or s.dtype.kind not in "iu":
-        raise KGLibraryError("jobs_from_stats: stats must be integers [n, 5] = (area, y1, x1, y2, x2)")
-    s = s.astype(np.int64)
-    box = np.where(s[:, :1] > 0, s[:, 1:], 0)
-    n = len(s)
-    return np.ascontiguousarray(np.concatenate([np.full((n, 1), int(img)), np.arange(1, n + 1)[:, None], box], 1).astype(np.int32)).reshape(-1, 6)
-
-
-def _counts(fn, n, nimg):
-    ns = [int(n)] if np.ndim(n) == 0 else [int(v) for v in n]
-    if len(ns) != nimg or any(v < 0 for v in ns):
-        raise KGLibraryError(f"{fn}: {len(ns)} instance count(s) for {nimg} label map(s)")
-    return ns
-
-
 def measure_host(labels, jobs_or_n, image=None):
     """labels: integers [H, W] or [nimg, H, W]; jobs_or_n: jobs [m, 6] = (img, id, y1, x1, y2, x2), or the instance count n (one per map
     for a stack): the ids 1 .. n are then measured inside their own boxes (labelmetrics.label_stats_host, which raises when a pixel lies
     outside [0, n]); image: None, or uint8 / uint16 [H, W, C] / [nimg, H, W, C] -> int64 [m, 10 + 4 C], one row per job, nothing split."""
-    maps = _side("measure_host", _labelmaps.host_maps("measure_host", labels, True)[0])
+    maps = _labelmaps.host_stack("measure_host", labels, SUMS_FIT)
     nimg, H, W = maps.shape
-    img = _host_image("measure_host", image, maps.shape)
+    img = _labelmaps.host_image("measure_host", image, maps.shape)
     C = 0 if img is None else img.shape[3]
-    if np.ndim(jobs_or_n) == 2:
-        jobs = _host_jobs("measure_host", jobs_or_n)
-    else:
-        ns = _counts("measure_host", jobs_or_n, nimg)
-        jobs = np.concatenate([jobs_from_stats(labelmetrics.label_stats_host(maps[i], ns[i]), i) for i in range(nimg)]).astype(np.int64)
+    jobs = _labelmaps.host_job_table("measure_host", maps, jobs_or_n, labelmetrics.label_stats_host)
     out = np.zeros((len(jobs), 10 + 4 * C), np.int64)
     for k, (i, v, y1, x1, y2, x2) in enumerate(jobs.tolist()):
         y1, x1, y2, x2 = max(y1, 0), max(x1, 0), min(y2, H), min(x2, W)
@@ -252,44 +198,18 @@ def combine_bands(rows, owner, n_jobs):
 
 # ---- device -----------------------------------------------------------------------------------------------------------------------------
 
-def _device_maps(fn, t):
-    t = _labelmaps.device_maps(fn, t, True)
-    return _side(fn, t.view((-1,) + t.shape[-2:]))
-
-
-def _device_image(fn, image, shape, dev):
-    """host array (uploaded once) or device tensor -> device tensor [nimg, H, W, C], or None"""
-    import torch
-    from . import ops
-    if image is None:
-        return None
-    if not torch.is_tensor(image):
-        a = _host_image(fn, image, shape)
-        if a.dtype == np.uint16:                                       # the bytes travel as int16; the kernel reads them unsigned
-            return ops.h2d(np.ascontiguousarray(a).view(np.int16), dev)
-        return ops.h2d(np.ascontiguousarray(a), dev)
-    t = image
-    if t.dtype not in (torch.uint8, torch.int16, getattr(torch, "uint16", torch.int16)) or t.device != dev:
-        raise KGLibraryError(f"{fn}: a device image must be uint8 or uint16 (int16 storage is read as uint16) on the maps' device")
-    if t.dim() == 3 and shape[0] == 1:
-        t = t[None]
-    if t.dim() != 4 or tuple(t.shape[:3]) != tuple(shape) or not 1 <= t.shape[3] <= MAX_CHANNELS:
-        raise KGLibraryError(f"{fn}: an image of {tuple(t.shape)} for label maps of {tuple(shape)}: [nimg, H, W, C] with 1 <= C <= {MAX_CHANNELS}")
-    return t.contiguous()
-
-
 def measure_rows(labels, jobs, image=None):
     """kg_label_measure as it is: labels device int32 [H, W] or [nimg, H, W]; jobs host int [m, 6] (uploaded once) or a device int32
     tensor; image None, a host array (uploaded once) or a device tensor -> device int64 [m, 10 + 4 C].  One launch, no copy back, no
     synchronisation, nothing split."""
     import torch
     from ._lib import ptr, stream_ptr
-    lab = _device_maps("measure", labels)
+    lab = _labelmaps.device_stack("measure", labels, SUMS_FIT)[0]
     dev = lab.device
     nimg, H, W = lab.shape
-    img = _device_image("measure", image, lab.shape, dev)
+    img = _labelmaps.device_image("measure", image, lab.shape, dev)
     C = 0 if img is None else img.shape[3]
-    jd = _labelmaps.device_jobs("measure", jobs, 6, _JOB_COLUMNS, dev)
+    jd = _labelmaps.device_jobs("measure", jobs, 6, JOB_COLUMNS, dev)
     m = jd.shape[0]
     out = torch.empty(m, 10 + 4 * C, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
@@ -308,25 +228,8 @@ def measure(labels, n=None, jobs=None, image=None, stats=None, max_job_pixels=65
     image: None, a host uint8 / uint16 array [H, W, C] / [nimg, H, W, C] (uploaded once) or a device tensor.
     A job whose box holds more than max_job_pixels pixels is measured in bands (split_jobs, combine_bands).
     ONE kg_label_measure launch, one upload (the jobs) and one device -> host copy (the rows)."""
-    lab = _device_maps("measure", labels)
-    nimg, H, W = lab.shape
-    if jobs is not None:
-        if n is not None or stats is not None:
-            raise KGLibraryError("measure: jobs cannot be given together with n / stats")
-        j = _host_jobs("measure", jobs)
-    else:
-        if n is None:
-            raise KGLibraryError("measure: the instance count n or a job table is needed")
-        ns = _counts("measure", n, nimg)
-        if stats is None:
-            per = [labelmetrics.label_stats(lab[i], ns[i]) for i in range(nimg)]
-        else:
-            per = [stats] if nimg == 1 and np.ndim(stats) == 2 else list(stats)
-            if len(per) != nimg or any(len(np.asarray(s)) != k for s, k in zip(per, ns)):
-                raise KGLibraryError(f"measure: stats must be [n, 5] per label map ({nimg} map(s), counts {ns})")
-        j = np.concatenate([jobs_from_stats(s, i) for i, s in enumerate(per)]).astype(np.int64)
-    # clamped first, so that the band rule sees the pixels a job really holds; a job of a bad image keeps its index and gets its zeros
-    j[:, 2:4] = np.clip(j[:, 2:4], 0, [H, W]); j[:, 4:6] = np.clip(j[:, 4:6], 0, [H, W])
+    lab = _labelmaps.device_stack("measure", labels, SUMS_FIT)[0]
+    j = _labelmaps.job_table("measure", lab, n, jobs, stats, labelmetrics.label_stats)
     pieces, owner = split_jobs(j, max_job_pixels)
     rows = measure_rows(lab, pieces, image).cpu().numpy()
     return Measurements(combine_bands(rows, owner, len(j)))
@@ -337,39 +240,26 @@ def measure_instances(inst, image=None, max_job_pixels=65536):
     with area_visible == 0 gets a row of zeros.  image: None, or uint8 / uint16 [H, W, C] at the label map's size (host array or device
     tensor).  A host label map (assemble_host's result) goes through measure_host."""
     import torch
-    from .instances import Instances
-    if not isinstance(inst, Instances):
-        raise KGLibraryError("measure_instances: an Instances or a TiledInstances")
-    stats = np.asarray(inst.table, np.int64).reshape(-1, 8)[:, 1:6]
-    if len(stats) != len(inst):
-        raise KGLibraryError(f"measure_instances: a table of {len(stats)} rows for {len(inst)} instances")
+    stats = _labelmaps.instance_stats("measure_instances", inst)
     if is_device(inst.labels):
         return measure(inst.labels, len(inst), image=image, stats=stats, max_job_pixels=max_job_pixels)
-    lab = inst.labels.numpy() if torch.is_tensor(inst.labels) else inst.labels
     if torch.is_tensor(image):
         image = image.cpu().numpy()
-    return Measurements(measure_host(lab, jobs_from_stats(stats), image))
+    return Measurements(measure_host(_labelmaps.host_labels(inst), jobs_from_stats(stats), image))
 
 
 def measure_instances_batch(insts, images=None, max_job_pixels=65536):
     """measure_instances for predict_instances' list (entries may be None), in place: every entry's `measurements` is set.  ONE launch for
     all images of one output size.  images: None (geometry only), or uint8 / uint16 [N, h, w, C] (host array or device tensor) with one
     image per entry, at the label maps' size."""
-    import torch
-    from .inference import size_groups
-    todo = [i for i, v in enumerate(insts) if v is not None]
     if images is not None and len(images) != len(insts):
         raise KGLibraryError(f"measure: {len(images)} images for {len(insts)} entries")
-    for _, members in size_groups([tuple(insts[i].labels.shape) for i in todo]):
-        idx = [todo[j] for j in members]
-        stack = torch.stack([insts[i].labels for i in idx])
+    for idx, stack, _, _ in _labelmaps.size_batches("measure_instances_batch", insts):
         img = None
         if images is not None:
             img = images[idx] if len(idx) != len(insts) else images
-        ns = [len(insts[i]) for i in idx]
-        got = measure(stack, ns, image=img, stats=[np.asarray(insts[i].table, np.int64)[:, 1:6] for i in idx], max_job_pixels=max_job_pixels)
-        r = 0
-        for i, k in zip(idx, ns):
-            insts[i].measurements = Measurements(got.raw[r:r + k])
-            r += k
+        got = measure(stack, [len(insts[i]) for i in idx], image=img, stats=[np.asarray(insts[i].table, np.int64)[:, 1:6] for i in idx],
+                      max_job_pixels=max_job_pixels)
+        for i, a, b in _labelmaps.deal(insts, idx):
+            insts[i].measurements = Measurements(got.raw[a:b])
     return insts

@@ -33,12 +33,12 @@ import math
 
 import numpy as np
 
-from . import _lib, _labelmaps, labelmetrics
-from ._labelmaps import instance_jobs as _instance_jobs, is_device
+from . import _lib, _labelmaps, distance, labelmetrics
+from ._labelmaps import MAX_SIDE, device_stack, host_stack  # noqa: F401  (MAX_SIDE: public here)
 from .labelmetrics import split_jobs
 
 KGLibraryError = _lib.KGLibraryError
-MAX_SIDE = 32768
+COUNTS_FIT = "the bound that keeps every count inside int64"       # what the side bound protects here
 MAX_SLOTS = 64
 _JOB_COLUMNS = "(img, id, y1, x1, y2, x2)"
 _ROW_JOB_COLUMNS = "(img, id, y1, x1, y2, x2, resume, after)"
@@ -56,13 +56,6 @@ def _slots(fn, slots):
     if isinstance(slots, (bool, np.bool_)) or not isinstance(slots, (int, np.integer)) or not 1 <= int(slots) <= MAX_SLOTS:
         raise KGLibraryError(f"{fn}: slots {slots!r} must be an integer in 1 .. {MAX_SLOTS}")
     return int(slots)
-
-
-def _side(fn, maps):
-    H, W = maps.shape[-2:]
-    if H > MAX_SIDE or W > MAX_SIDE:
-        raise KGLibraryError(f"{fn}: a map of {H} x {W} exceeds {MAX_SIDE} (the bound that keeps every count inside int64)")
-    return maps
 
 
 class Neighbours:
@@ -167,7 +160,7 @@ def neighbours_rows_host(labels, jobs, slots, connectivity=4):
     """kg_label_neighbours in NumPy: labels integers [H, W] or [nimg, H, W]; jobs integers [m, 8] = (img, id, y1, x1, y2, x2, resume, after)
     -> int64 [m, 2 + 3 slots] = {count, more, (value, sides, corners) x slots}, nothing split."""
     connectivity, slots = _connectivity("neighbours_rows_host", connectivity), _slots("neighbours_rows_host", slots)
-    maps = _side("neighbours_rows_host", _labelmaps.host_maps("neighbours_rows_host", labels, True)[0])
+    maps = host_stack("neighbours_rows_host", labels, COUNTS_FIT)
     nimg, H, W = maps.shape
     j = _labelmaps.host_jobs("neighbours_rows_host", jobs, 8, _ROW_JOB_COLUMNS).astype(np.int64)
     out = np.zeros((len(j), 2 + 3 * slots), np.int64)
@@ -184,21 +177,14 @@ def neighbours_rows_host(labels, jobs, slots, connectivity=4):
     return out
 
 
-def _host_job_table(fn, maps, jobs_or_n):
-    from .distance import _job_table
-    if np.ndim(jobs_or_n) == 2:
-        return _job_table(fn, maps, None, jobs_or_n, None, None)
-    return _job_table(fn, maps, jobs_or_n, None, None, labelmetrics.label_stats_host)
-
-
 def neighbours_host(labels, jobs_or_n, connectivity=4):
     """labels: integers [H, W] or [nimg, H, W]; jobs_or_n: jobs [m, 6] = (img, id, y1, x1, y2, x2), or the instance count n (one per map
     for a stack): the ids 1 .. n inside their own boxes (labelmetrics.label_stats_host, which raises when a pixel lies outside [0, n])
     -> Neighbours, one row per job: the full sorted list, not paged and not banded."""
     connectivity = _connectivity("neighbours_host", connectivity)
-    maps = _side("neighbours_host", _labelmaps.host_maps("neighbours_host", labels, True)[0])
+    maps = host_stack("neighbours_host", labels, COUNTS_FIT)
     nimg, H, W = maps.shape
-    j = _host_job_table("neighbours_host", maps, jobs_or_n)
+    j = _labelmaps.host_job_table("neighbours_host", maps, jobs_or_n, labelmetrics.label_stats_host)
     return Neighbours.from_lists([_job_list(maps[i], H, W, rest, connectivity) if 0 <= i < nimg else _NONE for i, *rest in j.tolist()])
 
 
@@ -242,11 +228,6 @@ def paged(row_fn, jobs, H, W, slots, max_job_pixels=65536):
 
 # ---- device -----------------------------------------------------------------------------------------------------------------------------
 
-def _device_maps(fn, t):
-    t = _labelmaps.device_maps(fn, t, True)
-    return _side(fn, t.view((-1,) + t.shape[-2:]))
-
-
 def neighbours_rows(labels, jobs, slots, connectivity=4):
     """kg_label_neighbours as it is: labels device int32 [H, W] or [nimg, H, W]; jobs host integers [m, 8] = (img, id, y1, x1, y2, x2,
     resume, after) (uploaded once) or a device int32 tensor -> device int64 [m, 2 + 3 slots].  One launch, no copy back, no
@@ -254,7 +235,7 @@ def neighbours_rows(labels, jobs, slots, connectivity=4):
     import torch
     from ._lib import ptr, stream_ptr
     connectivity, slots = _connectivity("neighbours", connectivity), _slots("neighbours", slots)
-    lab = _device_maps("neighbours", labels)
+    lab = device_stack("neighbours", labels, COUNTS_FIT)[0]
     nimg, H, W = lab.shape
     jd = _labelmaps.device_jobs("neighbours", jobs, 8, _ROW_JOB_COLUMNS, lab.device)
     m = jd.shape[0]
@@ -279,46 +260,33 @@ def neighbours(labels, n=None, jobs=None, stats=None, connectivity=4, slots=16, 
     A job whose box holds more than max_job_pixels pixels is listed in bands.  ONE kg_label_neighbours launch, one upload and one
     device -> host copy for all pieces, then one more of each per round for the pieces that have more than `slots` neighbours left
     (paged): with the default 16 slots an instance map needs one round."""
-    from .distance import _job_table
     connectivity, slots = _connectivity("neighbours", connectivity), _slots("neighbours", slots)
-    lab = _device_maps("neighbours", labels)
-    return _device_graph(lab, _job_table("neighbours", lab, n, jobs, stats, labelmetrics.label_stats), connectivity, slots, max_job_pixels)
+    lab = device_stack("neighbours", labels, COUNTS_FIT)[0]
+    return _device_graph(lab, _labelmaps.job_table("neighbours", lab, n, jobs, stats, labelmetrics.label_stats), connectivity, slots, max_job_pixels)
 
 
 # ---- Instances ----------------------------------------------------------------------------------------------------------------------------
 
 def _instance_graphs(insts, connectivity, expand, slots, max_job_pixels):
     """-> one Neighbours per entry (None for a None entry); the entries themselves are not touched"""
-    import torch
-    from . import distance
-    from .inference import size_groups
     connectivity, slots = _connectivity("neighbours_instances", connectivity), _slots("neighbours_instances", slots)
     grow = 0
     if expand is not None:
-        distance._square("neighbours_instances", expand)
+        distance.square("neighbours_instances", expand)
         grow = int(math.ceil(expand))
     out = [None] * len(insts)
-    todo = [i for i, v in enumerate(insts) if v is not None]
-    for i in todo:
-        distance._check_instances("neighbours_instances", insts[i])
-    host = [i for i in todo if not is_device(insts[i].labels)]
-    for i in host:
-        lab = insts[i].labels.numpy() if torch.is_tensor(insts[i].labels) else np.asarray(insts[i].labels)
+
+    def host_one(i, inst, lab):
         if expand is not None:
             lab = distance.expand_labels_host(lab, expand)
-        out[i] = neighbours_host(lab, _instance_jobs(insts[i], 0, grow, *lab.shape), connectivity)
-    todo = [i for i in todo if i not in host]
-    for (H, W), members in size_groups([tuple(insts[i].labels.shape) for i in todo]):
-        idx = [todo[k] for k in members]
-        stack = insts[idx[0]].labels[None] if len(idx) == 1 else torch.stack([insts[i].labels for i in idx])
+        out[i] = neighbours_host(lab, _labelmaps.instance_jobs(inst, 0, grow, *lab.shape), connectivity)
+    for idx, stack, H, W in _labelmaps.size_batches("neighbours_instances", insts, host_one):
         if expand is not None:
             stack = distance.expand_labels(stack, expand)
-        got = _device_graph(_device_maps("neighbours_instances", stack), np.concatenate([_instance_jobs(insts[i], k, grow, H, W) for k, i in enumerate(idx)]),
-                            connectivity, slots, max_job_pixels)
-        r = 0
-        for i in idx:
-            out[i] = got.slice(r, r + len(insts[i]))
-            r += len(insts[i])
+        got = _device_graph(device_stack("neighbours_instances", stack, COUNTS_FIT)[0], _labelmaps.batch_jobs(insts, idx, grow, H, W), connectivity, slots,
+                            max_job_pixels)
+        for i, a, b in _labelmaps.deal(insts, idx):
+            out[i] = got.slice(a, b)
     return out
 
 

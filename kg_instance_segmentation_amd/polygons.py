@@ -34,12 +34,11 @@ pixel to exactly one of them; fill(from_contours(contours(lab, ...))) gives lab 
 import numpy as np
 
 from . import _lib
-from ._labelmaps import is_device
+from ._labelmaps import MAX_SIDE, is_device
 
 KGLibraryError = _lib.KGLibraryError
 F = 256
 Q_MAX = 2 ** 29
-MAX_SIDE = 32768
 TILE_H, TILE_W = 32, 64                 # KG_POLY_TILE_H, KG_POLY_TILE_W of include/kgnet_hip.h
 EDGE_CHUNK = 256                        # KG_POLY_EDGE_CHUNK
 

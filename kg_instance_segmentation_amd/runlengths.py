@@ -40,19 +40,10 @@ Semantics (include/kgnet_hip.h is the normative text)
 import numpy as np
 
 from . import _lib, _labelmaps, labelmetrics
-from ._labelmaps import is_device
+from ._labelmaps import JOB_COLUMNS as _JOB_COLUMNS, MAX_SIDE, device_stack, host_stack, is_device, out_tensor  # noqa: F401  (MAX_SIDE: public here)
 
 KGLibraryError = _lib.KGLibraryError
-MAX_SIDE = 32768
-_JOB_COLUMNS = "(img, id, y1, x1, y2, x2)"
 _ROW_JOB_COLUMNS = "(img, id, y1, x1, y2, x2, head_at, tail_at)"
-
-
-def _side(fn, maps):
-    H, W = maps.shape[-2:]
-    if H > MAX_SIDE or W > MAX_SIDE:
-        raise KGLibraryError(f"{fn}: a map of {H} x {W} exceeds {MAX_SIDE}")
-    return maps
 
 
 def _size(fn, H, W):
@@ -161,14 +152,10 @@ def _job_ends(lab, H, W, job):
     return p[me & ~prev], p[me & ~nxt]
 
 
-def _maps(fn, labels):
-    return _side(fn, _labelmaps.host_maps(fn, labels, True)[0])
-
-
 def run_counts_host(labels, jobs):
     """kg_label_run_counts in NumPy: labels integers [H, W] or [nimg, H, W]; jobs integers [m, 6] = (img, id, y1, x1, y2, x2)
     -> int32 [m, 2] = {heads, tails}, nothing split."""
-    maps = _maps("run_counts_host", labels)
+    maps = host_stack("run_counts_host", labels)
     nimg, H, W = maps.shape
     j = _labelmaps.host_jobs("run_counts_host", jobs, 6, _JOB_COLUMNS).astype(np.int64)
     out = np.zeros((len(j), 2), np.int32)
@@ -182,7 +169,7 @@ def run_rows_host(labels, jobs, R, fill=0):
     """kg_label_runs in NumPy: jobs integers [m, 8] = (img, id, y1, x1, y2, x2, head_at, tail_at) -> int32 [R, 2], which starts as `fill`
     everywhere: the k-th head of a job stores p into out[head_at + k][0], the k-th tail into out[tail_at + k][1], each only when the slot
     lies in [0, R)."""
-    maps = _maps("run_rows_host", labels)
+    maps = host_stack("run_rows_host", labels)
     nimg, H, W = maps.shape
     j = _labelmaps.host_jobs("run_rows_host", jobs, 8, _ROW_JOB_COLUMNS).astype(np.int64)
     R = int(R)
@@ -215,20 +202,13 @@ def _paired(fn, per, first, last, H, W):
     return RunLengths(indptr, first, last, H, W)
 
 
-def _host_job_table(fn, maps, jobs_or_n):
-    from .distance import _job_table
-    if np.ndim(jobs_or_n) == 2 or (np.ndim(jobs_or_n) == 1 and np.size(jobs_or_n) == 0):        # an empty list is no jobs, as jobs=[] of runs
-        return _job_table(fn, maps, None, np.asarray(jobs_or_n, np.int64).reshape(-1, 6), None, None)
-    return _job_table(fn, maps, jobs_or_n, None, None, labelmetrics.label_stats_host)
-
-
 def runs_host(labels, jobs_or_n):
     """labels: integers [H, W] or [nimg, H, W]; jobs_or_n: jobs [m, 6] = (img, id, y1, x1, y2, x2), or the instance count n (one per map
     for a stack): the ids 1 .. n inside their own boxes (labelmetrics.label_stats_host, which raises when a pixel lies outside [0, n])
     -> RunLengths, one row per job, not banded."""
-    maps = _maps("runs_host", labels)
+    maps = host_stack("runs_host", labels)
     nimg, H, W = maps.shape
-    j = _host_job_table("runs_host", maps, jobs_or_n)
+    j = _labelmaps.host_job_table("runs_host", maps, jobs_or_n, labelmetrics.label_stats_host)
     ends = [_job_ends(maps[i], H, W, rest) if 0 <= i < nimg else _NONE for i, *rest in j.tolist()]
     cat = [np.concatenate([e[c] for e in ends]) if ends else np.zeros(0, np.int64) for c in range(2)]
     return _paired("runs_host", np.array([[len(e[0]), len(e[1])] for e in ends], np.int64).reshape(-1, 2), cat[0], cat[1], H, W)
@@ -257,18 +237,13 @@ def split_columns(jobs, max_job_pixels=65536):
 
 # ---- device -----------------------------------------------------------------------------------------------------------------------------
 
-def _device_maps(fn, t):
-    t = _labelmaps.device_maps(fn, t, True)
-    return _side(fn, t.view((-1,) + t.shape[-2:]))
-
-
 def run_counts(labels, jobs):
     """kg_label_run_counts as it is: labels device int32 [H, W] or [nimg, H, W]; jobs host integers [m, 6] = (img, id, y1, x1, y2, x2)
     (uploaded once) or a device int32 tensor -> device int32 [m, 2] = {heads, tails}.  One launch, no copy back, no synchronisation,
     nothing split."""
     import torch
     from ._lib import ptr, stream_ptr
-    lab = _device_maps("run_counts", labels)
+    lab = device_stack("run_counts", labels)[0]
     nimg, H, W = lab.shape
     jd = _labelmaps.device_jobs("run_counts", jobs, 6, _JOB_COLUMNS, lab.device)
     m = jd.shape[0]
@@ -284,17 +259,14 @@ def run_rows(labels, jobs, R, out=None):
     written in place: only the slots the table names change.  One launch, no copy back, no synchronisation, nothing split."""
     import torch
     from ._lib import ptr, stream_ptr
-    lab = _device_maps("run_rows", labels)
+    lab = device_stack("run_rows", labels)[0]
     nimg, H, W = lab.shape
     jd = _labelmaps.device_jobs("run_rows", jobs, 8, _ROW_JOB_COLUMNS, lab.device)
     m = jd.shape[0]
     R = int(R)
     if not 0 <= R <= 2 ** 31 - 1:
         raise KGLibraryError(f"run_rows: R {R}")
-    if out is None:
-        out = torch.zeros(R, 2, dtype=torch.int32, device=lab.device)
-    elif not is_device(out) or out.dtype != torch.int32 or tuple(out.shape) != (R, 2) or out.device != lab.device or not out.is_contiguous():
-        raise KGLibraryError(f"run_rows: out must be a contiguous int32 [{R}, 2] tensor on the maps' device")
+    out = torch.zeros(R, 2, dtype=torch.int32, device=lab.device) if out is None else out_tensor("run_rows", "out", out, (R, 2), torch.int32, lab.device)
     with torch.cuda.device(lab.device):
         _lib.call("kg_label_runs", ptr(lab), nimg, H, W, ptr(jd) if m else None, m, ptr(out) if R else None, R, stream_ptr())
     return out
@@ -331,36 +303,22 @@ def runs(labels, n=None, jobs=None, stats=None, max_job_pixels=65536):
     A job whose box holds more than max_job_pixels pixels is listed in column bands (split_columns).  ONE kg_label_run_counts launch and
     one small copy back, a host prefix over heads and tails, ONE kg_label_runs launch and one copy back: two launches and two copies
     whatever the map holds.  The rows that come back are checked (first <= last, ascending inside every job)."""
-    from .distance import _job_table
-    lab = _device_maps("runs", labels)
-    return _device_runs(lab, _job_table("runs", lab, n, jobs, stats, labelmetrics.label_stats), max_job_pixels)
+    lab = device_stack("runs", labels)[0]
+    return _device_runs(lab, _labelmaps.job_table("runs", lab, n, jobs, stats, labelmetrics.label_stats), max_job_pixels)
 
 
 # ---- Instances ----------------------------------------------------------------------------------------------------------------------------
 
 def _instance_runs(insts, max_job_pixels):
     """-> one RunLengths per entry (None for a None entry); the entries themselves are not touched"""
-    import torch
-    from . import distance
-    from .inference import size_groups
     out = [None] * len(insts)
-    todo = [i for i, v in enumerate(insts) if v is not None]
-    for i in todo:
-        distance._check_instances("runs_instances", insts[i])
-    host = [i for i in todo if not is_device(insts[i].labels)]
-    for i in host:
-        lab = insts[i].labels.numpy() if torch.is_tensor(insts[i].labels) else np.asarray(insts[i].labels)
-        out[i] = runs_host(lab, _labelmaps.instance_jobs(insts[i], 0, 0, *lab.shape))
-    todo = [i for i in todo if i not in host]
-    for (H, W), members in size_groups([tuple(insts[i].labels.shape) for i in todo]):
-        idx = [todo[k] for k in members]
-        stack = insts[idx[0]].labels[None] if len(idx) == 1 else torch.stack([insts[i].labels for i in idx])
-        got = _device_runs(_device_maps("runs_instances", stack), np.concatenate([_labelmaps.instance_jobs(insts[i], k, 0, H, W) for k, i in enumerate(idx)]),
-                           max_job_pixels)
-        r = 0
-        for i in idx:
-            out[i] = got.slice(r, r + len(insts[i]))
-            r += len(insts[i])
+
+    def host_one(i, inst, lab):
+        out[i] = runs_host(lab, _labelmaps.instance_jobs(inst, 0, 0, *lab.shape))
+    for idx, stack, H, W in _labelmaps.size_batches("runs_instances", insts, host_one):
+        got = _device_runs(device_stack("runs_instances", stack)[0], _labelmaps.batch_jobs(insts, idx, 0, H, W), max_job_pixels)
+        for i, a, b in _labelmaps.deal(insts, idx):
+            out[i] = got.slice(a, b)
     return out
 
 

@@ -36,7 +36,6 @@ Splitting only the suspicious instances: a merged pair is concave, so with hulls
 import numpy as np
 
 from . import _lib, _labelmaps, components, distance as _distance, labelmetrics, tiling
-from ._labelmaps import is_device
 
 KGLibraryError = _lib.KGLibraryError
 MAX_CELLS = 16384                       # KG_SP_CELLS of csrc/split.hip
@@ -232,14 +231,6 @@ def split_host(labels, n, distance, connectivity=4, min_seed_area=1, frame=False
 
 # ---- device -----------------------------------------------------------------------------------------------------------------------------
 
-def _stack(fn, labels):
-    t = _labelmaps.device_maps(fn, labels, True)
-    lab = t.view((-1,) + t.shape[-2:])
-    if max(lab.shape[1:]) > 32768:
-        raise KGLibraryError(f"{fn}: H, W at most 32768")
-    return lab, t.shape
-
-
 def regrow_rows(labels, seeds, jobs, connectivity=4):
     """kg_label_split as it is: labels, seeds device int32 [H, W] or [nimg, H, W]; jobs host integers [m, 8] = (img, id, y1, x1, y2, x2,
     nseeds, first_new) (uploaded once) or a device int32 tensor -> (out device int32 of the labels' shape, rows device int32 [m, 4] =
@@ -248,7 +239,7 @@ def regrow_rows(labels, seeds, jobs, connectivity=4):
     import torch
     from ._lib import ptr, stream_ptr
     conn, _ = _args("regrow", connectivity, 1)
-    lab, shape = _stack("regrow", labels)
+    lab, shape = _labelmaps.device_stack("regrow", labels)
     sd = _labelmaps.device_maps("regrow", seeds, True)
     if sd.shape != shape or sd.device != lab.device:
         raise KGLibraryError(f"regrow: seeds of {tuple(sd.shape)} for label maps of {tuple(shape)}: one shape and one device")
@@ -276,7 +267,7 @@ def regrow(labels, seeds, jobs, connectivity=4):
         raise KGLibraryError("regrow: rows that are no rows")
     large = np.flatnonzero(rows[:, 3]).tolist()
     if large:
-        lab, _ = _stack("regrow", labels)
+        lab, _ = _labelmaps.device_stack("regrow", labels)
         sd = seeds.contiguous().view(lab.shape)
         o3 = out.view(lab.shape)
         _, H, W = lab.shape
@@ -307,10 +298,9 @@ def seeds(labels, n, distance, connectivity=4, min_seed_area=1, frame=False):
     """seeds_host on the device: labels device int32 [H, W] with ids 1 .. n (or a stack [nimg, H, W] with one count per image) -> (the
     rank map, device int32 of the labels' shape; S host int64 [n], one array per image for a stack).  shrink_labels' launch, components 6,
     stats 3 (two copies back), remap 1."""
-    from .measure import _counts
     conn, msa = _args("seeds", connectivity, min_seed_area)
-    lab, shape = _stack("seeds", labels)
-    rank, S = _seeds_stack("seeds", lab, _counts("seeds", n, lab.shape[0]), distance, conn, msa, frame)
+    lab, shape = _labelmaps.device_stack("seeds", labels)
+    rank, S = _seeds_stack("seeds", lab, _labelmaps.counts("seeds", n, lab.shape[0]), distance, conn, msa, frame)
     return rank.view(shape), (S[0] if len(shape) == 2 else S)
 
 
@@ -320,14 +310,13 @@ def split_batch(labels, ns, distance, connectivity=4, min_seed_area=1, frame=Fal
     [nimg, H, W], per image the table, per image parent).  ONE seeds pass, ONE kg_label_split launch for all images, one kg_label_table
     launch per image and one copy back of all tables; an image without a table costs labelmetrics.label_stats on top."""
     import torch
-    from .measure import _counts
     conn, msa = _args("split", connectivity, min_seed_area)
     lab = _labelmaps.device_maps("split", labels, True)
     if lab.dim() != 3:
         raise KGLibraryError("split: a stack [nimg, H, W] and one instance count per image")
-    lab, _ = _stack("split", lab)
+    lab, _ = _labelmaps.device_stack("split", lab)
     nimg = lab.shape[0]
-    ns = _counts("split", ns, nimg)
+    ns = _labelmaps.counts("split", ns, nimg)
     for what, v in (("only", only), ("tables", tables)):
         if v is not None and len(v) != nimg:
             raise KGLibraryError(f"split: {what} must be None or one entry per image")
@@ -369,7 +358,7 @@ def _grown(inst, labels, table, parent):
     from .tiling import TiledInstances
     n = len(inst)
     if len(parent) == n:                                                  # nothing split: parent stays as it was
-        return components._like(inst, labels, table)
+        return components.like(inst, labels, table)
     old = np.arange(n, dtype=np.int32) if inst.parent is None else np.asarray(inst.parent, np.int32)
     dets = np.asarray(inst.dets)[parent]
     if isinstance(inst, TiledInstances):
@@ -393,26 +382,17 @@ def split_instances(inst, distance, connectivity=4, min_seed_area=1, frame=False
 def split_instances_batch(insts, distance, connectivity=4, min_seed_area=1, frame=False, only=None):
     """split_instances for predict_instances' list (entries may be None): the seeds and kg_label_split run ONCE over all images of one
     output size.  only: None, or per entry None or the ids that may be split."""
-    import torch
-    from .inference import size_groups
     _args("split_instances", connectivity, min_seed_area)
-    _distance._square("split_instances", distance)
+    _distance.square("split_instances", distance)
     if only is not None and len(only) != len(insts):
         raise KGLibraryError("split_instances: only must be None or one entry per instance list entry")
     only = [None] * len(insts) if only is None else list(only)
     out = list(insts)
-    todo = [i for i, v in enumerate(insts) if v is not None]
-    for i in todo:
-        _distance._check_instances("split_instances", insts[i])
-    host = [i for i in todo if not is_device(insts[i].labels)]
-    for i in host:
-        lab = insts[i].labels.numpy() if torch.is_tensor(insts[i].labels) else np.asarray(insts[i].labels)
-        new, table, parent = split_host(lab, len(insts[i]), distance, connectivity, min_seed_area, frame, only[i], insts[i].table)
-        out[i] = _grown(insts[i], new, table, parent)
-    todo = [i for i in todo if i not in host]
-    for _, members in size_groups([tuple(insts[i].labels.shape) for i in todo]):
-        idx = [todo[k] for k in members]
-        stack = insts[idx[0]].labels[None] if len(idx) == 1 else torch.stack([insts[i].labels for i in idx])
+
+    def host_one(i, inst, lab):
+        new, table, parent = split_host(lab, len(inst), distance, connectivity, min_seed_area, frame, only[i], inst.table)
+        out[i] = _grown(inst, new, table, parent)
+    for idx, stack, _, _ in _labelmaps.size_batches("split_instances", insts, host_one):
         new, tabs, parents = split_batch(stack, [len(insts[i]) for i in idx], distance, connectivity, min_seed_area, frame,
                                          [only[i] for i in idx], [insts[i].table for i in idx])
         for k, i in enumerate(idx):

@@ -31,8 +31,8 @@ Semantics (include/kgnet_hip.h is the normative text)
               through the same launch and their matrices are added on the host."""
 import numpy as np
 
-from . import _lib, _labelmaps, intensity, labelmetrics, measure
-from ._labelmaps import is_device
+from . import _lib, _labelmaps, labelmetrics, measure
+from ._labelmaps import check_cap, device_args, host_args, instance_stats, is_device, job_rows, job_table
 from .labelmetrics import split_jobs
 
 KGLibraryError = _lib.KGLibraryError
@@ -261,7 +261,7 @@ def glcm_rows_host(labels, jobs, image, levels=16):
     """labels: integers [H, W] or [nimg, H, W]; jobs: integers [m, 10] = (img, id, y1, x1, y2, x2, channel, distance, lo, span); image:
     uint8 / uint16 [H, W, C] / [nimg, H, W, C] -> int64 [m, 4, L, L].  From the definition: per job and direction the box and the box
     shifted by the offset are compared and their levels counted.  Nothing split."""
-    maps, img = intensity._host_args("glcm_rows_host", labels, image)
+    maps, img = host_args("glcm_rows_host", labels, image)
     j = _labelmaps.host_jobs("glcm_rows_host", jobs, 10, _JOB_COLUMNS).astype(np.int64)
     return _rows_host(maps, img, j, _levels("glcm_rows_host", levels))
 
@@ -286,14 +286,10 @@ def glcm_host(labels, jobs_or_n, image, levels=16, distance=1, channels=None, ra
     [nimg, H, W, C]; levels: L in 2 .. 32; distance: an integer in 1 .. 32 or a sequence of them; channels: None (all) or channel
     indices; range: None, (lo, hi), a list of such pairs per selected channel, or "object" (measure_host's min and max per job and
     channel) -> CoMatrices.  Nothing split."""
-    from .distance import _job_table
     fn = "glcm_host"
-    maps, img = intensity._host_args(fn, labels, image)
+    maps, img = host_args(fn, labels, image)
     L, ds, chans = _levels(fn, levels), _distances(fn, distance), _channels(fn, channels, img.shape[3])
-    if np.ndim(jobs_or_n) == 2:
-        j = _job_table(fn, maps, None, jobs_or_n, None, None)
-    else:
-        j = _job_table(fn, maps, jobs_or_n, None, None, labelmetrics.label_stats_host)
+    j = _labelmaps.host_job_table(fn, maps, jobs_or_n, labelmetrics.label_stats_host)
 
     def minmax():
         raw = measure.measure_host(maps, j, img)
@@ -309,15 +305,15 @@ def glcm_rows(labels, jobs, image, levels=16):
     """kg_label_glcm as it is: labels device int32 [H, W] or [nimg, H, W]; jobs host integers [m, 10] (uploaded once) or a device int32
     tensor; image a host array (uploaded once) or a device tensor -> device int32 [m, 4, L, L].  One launch, no copy back, no
     synchronisation, nothing split."""
-    lab, img = intensity._device_args("glcm_rows", labels, image)
+    lab, img = device_args("glcm_rows", labels, image)
     L = _levels("glcm_rows", levels)
     jd = _labelmaps.device_jobs("glcm_rows", jobs, 10, _JOB_COLUMNS, lab.device)
-    return intensity._rows("kg_label_glcm", lab, img, jd, (L,), (4, L, L))
+    return job_rows("kg_label_glcm", lab, img, jd, (L,), (4, L, L))
 
 
 def _device_glcm(fn, lab, img, j, L, ds, chans, rng, max_job_pixels, minmax=None):
     """lab, img: device tensors; j: clamped host jobs [m, 6]; minmax: None, or (min, max) [m, C] already known -> CoMatrices"""
-    cap = intensity._check_cap(fn, max_job_pixels)
+    cap = check_cap(fn, max_job_pixels)
 
     def measured():
         if minmax is not None:
@@ -341,13 +337,12 @@ def glcm(labels, n=None, jobs=None, image=None, levels=16, distance=1, channels=
     (measure.measure: one more launch and copy back).  A job above max_job_pixels pixels is cut into row bands (labelmetrics.split_jobs)
     whose pieces go through the same launch and are added on the host."""
     import torch
-    from .distance import _job_table
     fn = "glcm"
-    lab, img = intensity._device_args(fn, labels, image)
+    lab, img = device_args(fn, labels, image)
     L, ds, chans = _levels(fn, levels), _distances(fn, distance), _channels(fn, channels, img.shape[3])
     if torch.is_tensor(jobs):
         jobs = jobs.cpu().numpy()
-    return _device_glcm(fn, lab, img, _job_table(fn, lab, n, jobs, stats, labelmetrics.label_stats), L, ds, chans, range, max_job_pixels)
+    return _device_glcm(fn, lab, img, job_table(fn, lab, n, jobs, stats, labelmetrics.label_stats), L, ds, chans, range, max_job_pixels)
 
 
 # ---- Instances ----------------------------------------------------------------------------------------------------------------------------
@@ -365,44 +360,30 @@ def texture_instances(inst, image, levels=16, distance=1, channels=None, range=N
     visible pixel gets zeros (NaN once derived).  image: uint8 / uint16 [H, W, C] at the label map's size (host array or device tensor).
     range="object" takes the min and max from inst.measurements when they carry the image's intensity columns, and measures otherwise.
     A host label map (assemble_host's result) goes through glcm_host."""
-    import torch
-    from .distance import _job_table
     fn = "texture_instances"
-    stats = intensity._instance_stats(fn, inst)
+    stats = instance_stats(fn, inst)
     if is_device(inst.labels):
-        lab, img = intensity._device_args(fn, inst.labels, image)
+        lab, img = device_args(fn, inst.labels, image)
         L, ds, chans = _levels(fn, levels), _distances(fn, distance), _channels(fn, channels, img.shape[3])
-        j = _job_table(fn, lab, len(inst), None, stats, None)
+        j = job_table(fn, lab, len(inst), None, stats, None)
         return _device_glcm(fn, lab, img, j, L, ds, chans, range, max_job_pixels, _known_minmax(inst, img.shape[3]))
-    lab = inst.labels.numpy() if torch.is_tensor(inst.labels) else inst.labels
-    if torch.is_tensor(image):
-        image = image.cpu().numpy()
-        image = image.view(np.uint16) if image.dtype == np.int16 else image
-    return glcm_host(lab, measure.jobs_from_stats(stats), image, levels, distance, channels, range)
+    return glcm_host(_labelmaps.host_labels(inst), measure.jobs_from_stats(stats), _labelmaps.host_pixels(image), levels, distance, channels, range)
 
 
 def texture_instances_batch(insts, images, levels=16, distance=1, channels=None, range=None, max_job_pixels=65536):
     """texture_instances for predict_instances' list (entries may be None), in place: every entry's `texture` is set.  ONE kg_label_glcm
     launch for all images of one output size.  images: uint8 / uint16 [N, h, w, C] (host array or device tensor), one image per entry,
     at the label maps' size."""
-    import torch
-    from .distance import _job_table
-    from .inference import size_groups
     fn = "texture_instances_batch"
     if images is None or len(images) != len(insts):
         raise KGLibraryError(f"texture: {0 if images is None else len(images)} images for {len(insts)} entries")
-    todo = [i for i, v in enumerate(insts) if v is not None]
-    for _, members in size_groups([tuple(insts[i].labels.shape) for i in todo]):
-        idx = [todo[k] for k in members]
-        ns = [len(insts[i]) for i in idx]
-        lab, img = intensity._device_args(fn, torch.stack([insts[i].labels for i in idx]), images[idx] if len(idx) != len(insts) else images)
+    for idx, stack, _, _ in _labelmaps.size_batches(fn, insts):
+        lab, img = device_args(fn, stack, images[idx] if len(idx) != len(insts) else images)
         L, ds, chans = _levels(fn, levels), _distances(fn, distance), _channels(fn, channels, img.shape[3])
-        j = _job_table(fn, lab, ns, None, [intensity._instance_stats(fn, insts[i]) for i in idx], None)
+        j = job_table(fn, lab, [len(insts[i]) for i in idx], None, [instance_stats(fn, insts[i]) for i in idx], None)
         known = [_known_minmax(insts[i], img.shape[3]) for i in idx]
         minmax = None if any(k is None for k in known) else (np.concatenate([k[0] for k in known]), np.concatenate([k[1] for k in known]))
         got = _device_glcm(fn, lab, img, j, L, ds, chans, range, max_job_pixels, minmax)
-        r = 0
-        for i, k in zip(idx, ns):
-            insts[i].texture = CoMatrices(got.counts[r:r + k], ds, chans)
-            r += k
+        for i, a, b in _labelmaps.deal(insts, idx):
+            insts[i].texture = CoMatrices(got.counts[a:b], ds, chans)
     return insts
