@@ -831,6 +831,52 @@ int kg_label_split(const int* labels, const int* seeds, int nimg, int H, int W, 
  * 2-byte image) and never synchronises. */
 int kg_label_glcm(const int* labels, int nimg, int H, int W, const void* image, int channels, int elem_bytes, const int* jobs, int m,
                   int levels, int* out, void* stream);
+/* Instance midlines (csrc/thinning.hip; thinning.py states the semantics in NumPy as thin_host / midlines_host): the topological
+ * skeleton of every instance by exact parallel thinning, and the length, tips and branch points read from it -- what an object with
+ * processes (a neural cell, a leaf on its petiole) is measured by.  It is called thinning / midlines everywhere: "skeleton" already means
+ * the keypoint skeleton of the post-processing.  Everything is an exact integer.
+ * JOB.  {img, id, y1, x1, y2, x2}, a half-open box clamped to the map.  P = the pixels of the clamped box in image img with labels == id.
+ * Everything outside the clamped box is background, so a box that cuts an object thins the cut part.  Values are compared only: 0, -1,
+ * INT_MIN and INT_MAX are ordinary ids.  H, W <= 32768 as for kg_label_measure.
+ * NEIGHBOURS.  Named clockwise from north, y growing downward: P2 = N, P3 = NE, P4 = E, P5 = SE, P6 = S, P7 = SW, P8 = W, P9 = NW.
+ * PASS.  One pass is two sub-iterations.  Each is fully synchronous: every decision reads the state at the start of the sub-iteration.
+ * A set pixel is deleted iff C == 1 and 2 <= N <= 3 and m == 0, where
+ *   C  = (!P2 & (P3|P4)) + (!P4 & (P5|P6)) + (!P6 & (P7|P8)) + (!P8 & (P9|P2))
+ *   N1 = (P9|P2) + (P3|P4) + (P5|P6) + (P7|P8)
+ *   N2 = (P2|P3) + (P4|P5) + (P6|P7) + (P8|P9)
+ *   N  = min(N1, N2)
+ *   m  = (P6 | P7 | !P9) & P8        in the first sub-iteration
+ *   m  = (P2 | P3 | !P5) & P4        in the second
+ * (Guo-Hall's parallel thinning with OpenCV's order of the sub-iterations).  Passes repeat until one deletes nothing, or max_passes
+ * have run (max_passes >= 1; 0 means no limit; a negative value is refused).  passes = the number of passes that deleted something.
+ * S is what remains: a subset of P with P's 8-connected components and P's 4-connected background components, and -- without a limit --
+ * a fixed point of the rule.  Thinning stopped after k passes is an erosion that never deletes a component and never opens or closes
+ * a hole.  Pinned by the host statement: a 2 x 2 square leaves its upper-right pixel in 1 pass; a 7 x 54 bar leaves the 48 pixels of
+ * its middle row, three in from either end, in 3 passes; an 8 x 8 checkerboard is a fixed point (0 passes).
+ * ROW.  rows = device int32 [m][9] = {members, pixels, isolated, ends, junctions, ortho, diag, passes, status}, every element written,
+ * counted on S with 8-neighbourhoods inside S: members = |P|; pixels = |S|; isolated = pixels without a neighbour; ends = pixels with
+ * exactly one neighbour; junctions = pixels with at least three 0 -> 1 transitions in the cyclic sequence P2 .. P9; ortho = the
+ * unordered pairs of S pixels that share a side; diag = the unordered diagonal pairs neither of whose two common side-neighbours is in
+ * S (a diagonal that an L already bridges is no edge).  The midline's length is ortho + sqrt(2) * diag, taken on the host in float64.
+ * status 0 is ok; status 1: the box does not fit (SIZE), the other columns are 0 and nothing is stored for the job.  A bad job -- an
+ * image index outside [0, nimg), an empty or inverted box -- gets a row of zeros with status 0; an id the box does not hold likewise.
+ * Example: in a 16 x 21 map, id 1 on rows 2..4 x columns 2..18 plus rows 5..13 x columns 9..11 gives {78, 23, 0, 3, 1, 20, 2, 2, 0};
+ * S is row 3 without column 10, plus column 10 on rows 4..12.
+ * MAP.  skel = device int32 [nimg][H][W], not overlapping labels: id on the pixels of S of every job, 0 elsewhere.  The entry zeroes it
+ * on the stream first, the kernel then stores id on S and nothing else, so every element is written.  It is a label map: every other
+ * entry of the family works on it unchanged.  Jobs of one id whose boxes overlap store the union of their results.
+ * SIZE.  A job is thinned on the device when one bit per pixel with a one-pixel zero halo fits 16 KiB of LDS (two such bitmaps, 32 KiB
+ * per workgroup): with h, w the clamped box and pw = ceil((w + 2) / 32) words per row, (h + 2) * pw <= 4096 -- 126 x 126, 254 x 510 and
+ * 4094 x 30 fit, 255 x 510 does not.  Thinning cannot be banded, so thinning.py thins such a box on the host from that box copied back
+ * and writes it in.
+ * INDEX RULE.  No new exception.  The job table is the one device-read table: box clamped before any address is formed, image index only
+ * inside (unsigned)img < (unsigned)nimg.  Every LDS index is a box-local coordinate plus a fixed offset inside the halo; the predicate of
+ * the store is an LDS bit and its address a box coordinate: no LDS or global address depends on a label.  No atomics, no global scratch.
+ * One clear and ONE launch whatever m is (one workgroup of 256 per job, the grid strides beyond 2^20 jobs and zeroes both bitmaps per
+ * job); m == 0 launches only the clear (jobs and rows may then be NULL).  Validates on the host before any HIP call (null pointers, nimg,
+ * H, W > 0, the size rules, max_passes >= 0, m >= 0, 4-byte alignment, skel not overlapping labels, rows not overlapping a map, jobs not
+ * overlapping skel or rows) and never synchronises. */
+int kg_label_thin(const int* labels, int nimg, int H, int W, const int* jobs, int m, int max_passes, int* skel, int* rows, void* stream);
 
 /* ---- per-box segmentation branch (KGnet.py:246-267, 321-350): ragged row bookkeeping ---- */
 int kg_seg_build_rows(const int* boxtab8, int nb, int* rowdesc, int* row2box, int* srcrow, void* stream);

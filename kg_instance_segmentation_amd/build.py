@@ -55,6 +55,7 @@ SOURCES = {
     "intensity.hip": [],
     "split.hip": [],
     "texture.hip": [],
+    "thinning.hip": [],
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function"]

@@ -1,6 +1,6 @@
 // label_common.h -- what the label-map kernels share (instances.hip, tiling.hip, labelmetrics.hip, components.hip, measure.hip,
-// distance.hip, neighbours.hip, runlengths.hip, contours.hip, polygons.hip, hulls.hip, intensity.hip, split.hip, texture.hip; paste.hip
-// for the bit-mask leading dimension): wave reductions, the clamped job box and its walk, the block combine of four wave partials, the
+// distance.hip, neighbours.hip, runlengths.hip, contours.hip, polygons.hip, hulls.hip, intensity.hip, split.hip, texture.hip,
+// thinning.hip; paste.hip for the bit-mask leading dimension): wave reductions, the clamped job box and its walk, the block combine of four wave partials, the
 // row-segment run walk, per-image ranges passed by value, and the host argument checks -- among them the side bound KG_LABEL_MAX_SIDE,
 // the block that opens a per-job entry (kg_check_job_stack), the image check (kg_check_image) and the overlap test (kg_apart).
 // Integers only, plain C++ and vector memory operations only.
@@ -33,7 +33,8 @@
 //     int [4][1024] with L <= 32; its staged bytes are indexed by box-local coordinates alone.
 // Labels and pixel values are otherwise predicates, summands and stored values only.  kg_label_split (split.hip) adds NO exception: its
 // LDS state is indexed by box-local coordinates alone, never by a label, a seed or a rank, and nseeds / first_new of its job table are a
-// predicate bound and a stored value.
+// predicate bound and a stored value.  kg_label_thin (thinning.hip) adds NO exception either: its two LDS bitmaps are indexed by box-local
+// coordinates alone (plus a fixed offset inside the zero halo), the predicate of its store is an LDS bit and the address a box coordinate.
 #pragma once
 #include "kg_common.h"
 #include <limits.h>

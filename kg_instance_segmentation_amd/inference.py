@@ -112,7 +112,7 @@ def instances_from_predictions(preds):
 
 
 def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None, max_workspace_bytes=None, clean=None, measure=None,
-                      expand=None, neighbours=None, runs=None, contours=None, hulls=None, quantiles=None, split=None, texture=None):
+                      expand=None, neighbours=None, runs=None, contours=None, hulls=None, quantiles=None, split=None, texture=None, thin=None):
     """predict(packed=True) followed by the instance label map and the per-instance table of every image (instances.py), on the device:
     the label map (4 bytes per pixel) and the table (64 bytes per instance) replace n full-size masks as what crosses to the host.
     clean: None, or a dict of components.clean's policy arguments: every label map is then cleaned on the device (one components pass
@@ -147,7 +147,11 @@ def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None
     min_seed_area, frame, only): merged instances are then split into their core seeds' regions (split.py), after the clean-up and
     before the expansion and everything else; every result has `parent` set, dets extended by a copy of the parent's row per new id and
     masks unchanged.  One seeds pass and one kg_label_split launch for all images of one output size.  None adds no launch and no
-    import."""
+    import.
+    thin: None; True, or a dict of thinning.thin_instances_batch's keyword arguments (max_passes): every result's `midlines` holds the
+    midline of its instances (thinning.py: length, tips, branch points, and the midline map `skel`), taken next to the other
+    measurements on the final label map -- one upload, one launch and one copy back for all images of one output size.  None adds no
+    launch and no import."""
     if not torch.is_tensor(x) or x.device.type != "cuda":
         raise _lib.KGLibraryError("predict_instances (MI355X build) needs the input batch on a GPU device")
     out = instances_from_predictions(predict(model, x, nms_thresh, seg_thresh, image_sizes, max_workspace_bytes=max_workspace_bytes, packed=True))
@@ -171,6 +175,9 @@ def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None
         from . import texture as _texture
         kw = dict(texture) if isinstance(texture, dict) else {"image": texture}
         _texture.texture_instances_batch(out, kw.pop("image", None), **kw)
+    if thin is not None and thin is not False:
+        from . import thinning
+        thinning.thin_instances_batch(out, **({} if thin is True else dict(thin)))
     if neighbours is not None and neighbours is not False:
         from . import neighbours as _neighbours
         _neighbours.neighbours_instances_batch(out, **({} if neighbours is True else dict(neighbours)))

@@ -217,8 +217,8 @@ class TiledInstances(Instances):
     """predict_tiled's result: labels = device int32 [H, W] (assemble_host: a NumPy array); dets = float32 [n, 5] (y1, x1, y2, x2, conf) in
     global pixels, clipped to the image, in id order; table = host int64 [n, 8]; masks = None; tile int32 [n]; origin int32 [n, 2];
     tile_masks = the tile-local mask rows in id order (BitMasks; assemble_host: uint8 [n, th, tw]): tile_masks[i] placed at origin[i]
-    is the full mask of instance i + 1.  measurements, neighbours, runs, contours, hulls, quantiles and texture are Instances': None unless
-    asked for (measure=, neighbours=, runs=, contours=, hulls=, quantiles=, texture= of predict_tiled).  parent is Instances' too: None unless a split ran
+    is the full mask of instance i + 1.  measurements, neighbours, runs, contours, hulls, quantiles, texture and midlines are Instances': None unless
+    asked for (measure=, neighbours=, runs=, contours=, hulls=, quantiles=, texture=, thin= of predict_tiled).  parent is Instances' too: None unless a split ran
     (split=, split.py); then dets, tile and origin hold a copy of the parent's row for every new id and tile_masks keeps the rows of the
     parents only: tile_masks[parent[i]] placed at origin[i] is the mask instance i + 1 came from."""
     __slots__ = ("tile", "origin", "tile_masks")
@@ -487,7 +487,7 @@ def assemble(plan, per_tile_preds, nms_thresh=0.5, device=None, stage=None, clea
 
 
 def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thresh=0.5, seg_thresh=0.5, max_workspace_bytes=None, stage=None,
-                  clean=None, measure=False, expand=None, neighbours=None, runs=None, contours=None, hulls=None, quantiles=None, split=None, texture=None):
+                  clean=None, measure=False, expand=None, neighbours=None, runs=None, contours=None, hulls=None, quantiles=None, split=None, texture=None, thin=None):
     """Instance segmentation of a whole image at native resolution -> TiledInstances.  image: host uint8 [H, W, 3] (uploaded once, to the
     model's device) or a device uint8 tensor; tile: the network input size, (th, tw) or one int, multiples of 32; overlap: pixels two
     neighbouring tiles share at least (choose it at least as large as the largest object: an object is cut at the edge of the tile that
@@ -519,7 +519,11 @@ def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thres
     split: None; a distance in pixels (1 .. 64), or a dict of split.split_instances' arguments (distance, connectivity, min_seed_area,
     frame, only): merged instances of the STITCHED map are then split into their core seeds' regions (split.py, through assemble), after
     the clean-up and before the expansion and everything else; the result has `parent` set, dets / tile / origin extended by a copy of
-    the parent's row per new id and tile_masks unchanged.  None adds no launch and no import."""
+    the parent's row per new id and tile_masks unchanged.  None adds no launch and no import;
+    thin: None; True, or a dict of thinning.thin_instances' keyword arguments (max_passes): the result's `midlines` then holds the midline
+    of the instances of the STITCHED map (thinning.py: length, tips, branch points, and the midline map `skel`; no tile seams), taken
+    next to the other measurements on the final label map -- one more upload, launch and copy back.  None adds no launch and no
+    import."""
     import torch
     from . import inference
     quantiles = None if quantiles is False else quantiles
@@ -557,6 +561,9 @@ def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thres
         from . import texture as _texture
         kw = {} if texture is True else dict(texture)
         out.texture = _texture.texture_instances(out, kw.pop("image", image), **kw)
+    if thin is not None and thin is not False:
+        from . import thinning
+        out.midlines = thinning.thin_instances(out, **({} if thin is True else dict(thin)))
     if neighbours is not None and neighbours is not False:
         from . import neighbours as _neighbours
         out.neighbours = _neighbours.neighbours_instances(out, **({} if neighbours is True else dict(neighbours)))
