@@ -246,7 +246,18 @@ int kg_seg_loss(const float* prob, const void* tgt_u8, const int* patches, const
  * phase boundaries on its own stream; end waits and returns the summed milliseconds {Hough vote, Gaussian, peaks + ranking, grouping} */
 int kg_postproc_timing_begin(void);
 int kg_postproc_timing_end(float* ms4);
-/* ---- post-processing in float64, bit-identical to postprocessing.py:16-261 and nms.py:4-53 ---- */
+/* ---- post-processing in float64, bit-identical to postprocessing.py:16-261 and nms.py:4-53 ----
+ * Capacities (kg_postproc_scale and, per image, kg_postproc_batch; tests/test_gpu_detect.py part D).  With T = the peaks of the map:
+ *   npeaks_out                   T, the full count, whatever peak_cap is
+ *   peaks_out, peak_conf_out     [3][peak_cap] (ids | xs | ys) and [peak_cap]: the first min(T, peak_cap) peaks in scan order (channel, then
+ *                                row, then column); the entries behind them are unspecified.  Later peaks are dropped without an error.
+ *   ranking, grouping            see those min(T, peak_cap) peaks only: the result is the reference's grouping of the truncated list
+ *   nskel                        the skeletons formed, which may exceed skel_cap: rows [0, min(nskel, skel_cap)) of skel are written, none
+ *                                beyond.  Up to 8192 ranked peaks on a map of at most 1024 x 1024 this is the full count of the reference's
+ *                                grouping.  On larger inputs a skeleton beyond skel_cap is not remembered and cannot suppress a later seed near
+ *                                it: once nskel > skel_cap it need not be the reference's count any more (the first skel_cap rows are exact either way).
+ * kg_skeleton_boxes reads min(nskel, skel_cap) rows and adds the boxes it forms to nbox; rows at or beyond box_cap are dropped, nbox still
+ * counts them, and a later appending call then writes nothing.  kg_nms reads min(nbox, box_cap) rows. */
 long kg_postproc_workspace_bytes(int H, int W, int peak_cap, int skel_cap);
 int kg_postproc_scale(const float* kp, const float* soff, const float* mid, int H, int W, double thresh, void* ws,
                       long ws_bytes, int peak_cap, int skel_cap, double* skel, int* nskel, double* heat_out,

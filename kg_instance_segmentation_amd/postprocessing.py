@@ -28,6 +28,8 @@ class _Workspace:
 
 
 def caps(H, W):
+    """(peak_cap, skel_cap) of an H x W map.  Beyond 65 536 peaks per map the later peaks in scan order (channel, row, column) are dropped
+    without an error."""
     peak_cap = min(5 * H * W, 1 << 16)
     return peak_cap, peak_cap
 
