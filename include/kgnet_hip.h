@@ -888,6 +888,43 @@ int kg_label_glcm(const int* labels, int nimg, int H, int W, const void* image, 
  * H, W > 0, the size rules, max_passes >= 0, m >= 0, 4-byte alignment, skel not overlapping labels, rows not overlapping a map, jobs not
  * overlapping skel or rows) and never synchronises. */
 int kg_label_thin(const int* labels, int nimg, int H, int W, const int* jobs, int m, int max_passes, int* skel, int* rows, void* stream);
+/* Boundary distances between two label maps (csrc/boundaries.hip; boundaries.py states the semantics in NumPy as border_d2_host): for
+ * every source pixel of one instance the exact squared distance to the nearest outline pixel of an instance of ANOTHER map.  Hausdorff,
+ * HD95, ASSD and the surface Dice are host float64 over these integers.  Every distance is an exact integer.
+ * MAPS.  a, b = device int32 [nimg][H][W], one shape, one device, H, W <= 32768 as for kg_label_measure, nimg * H * W <= 2^31 - 1.  Values
+ * are compared only: 0, -1, INT_MIN and INT_MAX are ordinary ids.  a and b may be the same map.
+ * BORDER PIXEL of id v in a map.  A pixel that holds v and has at least one of its four side-neighbours either outside the map or holding
+ * another value.  The neighbours are read from the MAP, never from a box, and a position outside the map is decided by a predicate on
+ * its coordinates before its address exists.  It is mask & ~binary_erosion(mask) with the 4-connected cross and a border value of 0.
+ * JOB.  int32 [13] = {img, dir, id_s, sy1, sx1, sy2, sx2, id_t, ty1, tx1, ty2, tx2, first}.  dir == 0 takes the sources from a and the
+ * targets from b, dir != 0 the other way round; dir is a predicate only.  Both boxes are half-open and clamped to the map before any
+ * address is formed.
+ * MODE.  Two bits.  Bit 0, sources: 0 = the border pixels of id_s inside the clamped source box, 1 = all pixels of id_s inside it.
+ * Bit 1, targets: 0 = border (surface to surface, the medpy / MONAI convention), 2 = region (GlaS).
+ * SOURCES S.  As the mode says, in raster order of the source box.  TARGETS T.  The border pixels of id_t inside the clamped target box,
+ * always.
+ * VALUE.  d2(s) = min over t in T of (ys - yt)^2 + (xs - xt)^2.  In region mode d2(s) = 0 when s lies inside the clamped target box and
+ * the target map holds id_t at s.  When T is empty and the region rule does not apply, d2(s) = -1.  d2 fits int32: 2 * 32767^2 < 2^31.
+ * Because borders are read from the map and a minimum is taken, pieces compose exactly: the sources of bands of whole rows that tile a
+ * source box, in ascending y, concatenate to the box's; the values of rectangles that tile a target box merge by the element-wise
+ * minimum with -1 as +infinity (the region rule gives 0 in the one rectangle that holds s).
+ * SIZE RULE.  The clamped target box of a job holds at most KG_BORDER_MAX_TARGET_PIXELS = 8192 pixels, so every target fits one 32 KiB
+ * LDS list of box-local (y << 16 | x) words whatever the map holds; the boxes alone decide it.  A job that breaks the rule gets the
+ * count {0, 0} with status 1 and stores nothing.  The source box has no bound: it is streamed.
+ * BAD JOBS.  An image index outside [0, nimg), or an empty or inverted box on either side: counts {0, 0, 0}, nothing stored.
+ * kg_label_border_counts: counts = device int32 [m][3] rows {n_sources, n_targets, status}, every element written; `first` is ignored.
+ * kg_label_border_d2: d2 = device int32 [D], D <= 2^31 - 1.  The d2 of the k-th source of job j is stored at d2[first_j + k], only
+ * inside the 64-bit unsigned predicate first_j + k < D: a negative or oversized first from a wrong table gives wrong values and cannot
+ * leave the buffer.  With first = the exclusive prefix sum of n_sources and D = their total every element is written.
+ * INDEX RULE.  The d2 slot is of the kg_label_runs kind (an offset of the job table plus a prefix count of predicates); no other
+ * exception.  LDS is indexed by compaction counts and holds coordinates, never a label.  No atomics, no global scratch.
+ * One launch per entry whatever m is (one workgroup of 256 per job, the grid strides beyond 2^20 jobs); m == 0 launches nothing (jobs
+ * and the output may then be NULL), and so does D == 0.  Both validate on the host before any HIP call (null pointers, nimg, H, W > 0,
+ * the size rules of both maps, m >= 0, mode in 0 .. 3, D >= 0, 4-byte alignment, the output overlapping neither a map nor the jobs) and
+ * never synchronise. */
+#define KG_BORDER_MAX_TARGET_PIXELS 8192
+int kg_label_border_counts(const int* a, const int* b, int nimg, int H, int W, const int* jobs, int m, int mode, int* counts, void* stream);
+int kg_label_border_d2(const int* a, const int* b, int nimg, int H, int W, const int* jobs, int m, int mode, int* d2, int D, void* stream);
 
 /* ---- per-box segmentation branch (KGnet.py:246-267, 321-350): ragged row bookkeeping ---- */
 int kg_seg_build_rows(const int* boxtab8, int nb, int* rowdesc, int* row2box, int* srcrow, void* stream);

@@ -56,6 +56,7 @@ SOURCES = {
     "split.hip": [],
     "texture.hip": [],
     "thinning.hip": [],
+    "boundaries.hip": [],
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function"]

@@ -1,6 +1,6 @@
 // label_common.h -- what the label-map kernels share (instances.hip, tiling.hip, labelmetrics.hip, components.hip, measure.hip,
 // distance.hip, neighbours.hip, runlengths.hip, contours.hip, polygons.hip, hulls.hip, intensity.hip, split.hip, texture.hip,
-// thinning.hip; paste.hip for the bit-mask leading dimension): wave reductions, the clamped job box and its walk, the block combine of four wave partials, the
+// thinning.hip, boundaries.hip; paste.hip for the bit-mask leading dimension): wave reductions, the clamped job box and its walk, the block combine of four wave partials, the
 // row-segment run walk, per-image ranges passed by value, and the host argument checks -- among them the side bound KG_LABEL_MAX_SIDE,
 // the block that opens a per-job entry (kg_check_job_stack), the image check (kg_check_image) and the overlap test (kg_apart).
 // Integers only, plain C++ and vector memory operations only.
@@ -17,7 +17,8 @@
 //     and the store happens only inside the 64-bit unsigned predicate slot < R.  (kg_runs_paint reads a row only at a binary-search
 //     position in [0, R).)  kg_label_contours (contours.hip) stores the same way: ring slot and vertex offset are offsets of the job
 //     table plus prefix counts, inside slot < R and first + k < V; and so does kg_label_hulls (hulls.hip): the vertex slot is vert_at of
-//     the job table plus a prefix count, inside k < cap and vert_at + k < V;
+//     the job table plus a prefix count, inside k < cap and vert_at + k < V; the d2 slot of kg_label_border_d2 (boundaries.hip) is of
+//     this kind too: first of the job table plus a prefix count, inside first + k < D;
 //   - the tracer of contours.hip: its position is an LDS bit index that depends on bits derived from labels.  It is bounded by
 //     construction (a crack touches a P pixel of the box) and by an explicit clamp to [0, h] x [0, w] after every step.  No GLOBAL
 //     address depends on a label there either;

@@ -9,7 +9,8 @@ every ground-truth id, and the pixel count of every (predicted id, GT id) pair t
     candidate_pairs  the id pairs whose boxes overlap, with the box they share (host)
     contingency      the pixel count of every candidate pair inside that box (kg_label_inter_jobs), pairs that do not meet dropped
     match / kaggle_score / panoptic / aji / dice   pure host float64 over a Contingency
-    LabelEvaluator   accumulates them over images; evaluate_tiled(model, samples) runs predict_tiled and scores every image
+    LabelEvaluator   accumulates them over images; evaluate_tiled(model, samples) runs predict_tiled and scores every image;
+                     boundary= adds the boundary distances of the true-positive pairs (boundaries.py): hd, hd95, assd, nsd
 
 The *_host functions state the same semantics in NumPy (the CPU route, and the yardstick of the GPU tests); every count is an exact integer.
 
@@ -21,6 +22,8 @@ Semantics
   bands       a job whose box holds more than max_job_pixels pixels is split on the host into bands of whole rows (of row pieces, for a
               box wider than max_job_pixels) of at most that many pixels; the band counts are added on the host in int64.
   iou         I / (A_p + A_g - I) in float64; a pair that does not meet has 0."""
+import math
+
 import numpy as np
 
 from . import _lib, evaluation, instances, polygons
@@ -319,8 +322,13 @@ def _is_map_pair(v):
 class LabelEvaluator:
     """Accumulates the label-map metrics over images: add(pred, gt) per image, summary() at the end."""
 
-    def __init__(self, thresholds=evaluation.THRESHOLDS, use_07_metric=False):
+    def __init__(self, thresholds=evaluation.THRESHOLDS, use_07_metric=False, boundary=None):
+        """boundary: None (overlap metrics only), True, or dict(tolerance=2, sources='border', targets='border'): add() then also runs
+        boundaries.pair_distances on the true-positive pairs of panoptic (IoU > 0.5), on whichever side the maps live, and summary() gains
+        hd, hd95, assd, nsd (at the tolerance) and boundary_pairs."""
         self.thresholds = np.asarray(thresholds, np.float64).reshape(-1)
+        self.boundary = self._boundary_options(boundary)
+        self.distances = {"hd": [], "hd95": [], "assd": [], "nsd": []}   # one value per true-positive pair added
         self.use_07_metric = use_07_metric
         self.seg = evaluation._Stream(len(self.thresholds))
         self.scores = []                                             # kaggle image scores
@@ -328,6 +336,30 @@ class LabelEvaluator:
         self.aji = []
         self.dice = [0, 0]
         self.images = 0
+
+    @staticmethod
+    def _boundary_options(boundary):
+        if boundary is None or boundary is False:
+            return None
+        opts = {"tolerance": 2, "sources": "border", "targets": "border"}
+        if boundary is not True:
+            if not isinstance(boundary, dict) or set(boundary) - set(opts):
+                raise KGLibraryError(f"LabelEvaluator: boundary must be None, True or a dict with keys among {sorted(opts)}")
+            opts.update(boundary)
+        from . import boundaries
+        boundaries.mode_of("LabelEvaluator", opts["sources"], opts["targets"])
+        if not float(opts["tolerance"]) >= 0:
+            raise KGLibraryError(f"LabelEvaluator: boundary tolerance {opts['tolerance']!r}")
+        return opts
+
+    def _add_boundary(self, plab, glab, c, pred_stats, gt_stats, on_device):
+        """The boundary distances of the true-positive pairs of one image (panoptic's: IoU > 0.5), where the maps live"""
+        from . import boundaries
+        o = self.boundary
+        route = boundaries.pair_distances if on_device else boundaries.pair_distances_host
+        d = route(plab, glab, c.pairs[c.iou() > 0.5], pred_stats, gt_stats, sources=o["sources"], targets=o["targets"])
+        for key, v in (("hd", d.hausdorff()), ("hd95", d.hd95()), ("assd", d.assd()), ("nsd", d.nsd(o["tolerance"]))):
+            self.distances[key].extend(v.tolist())
 
     def add(self, pred, gt, conf=None):
         """pred: an Instances / TiledInstances (its label map, its table as the stats, its dets' confidences), or a (labels, n_pred) pair,
@@ -360,12 +392,19 @@ class LabelEvaluator:
             glab, n_gt, gt_stats = self._device_gt(gt, plab.device)
             if tuple(glab.shape) != shape:
                 raise KGLibraryError(f"LabelEvaluator.add: a predicted map of {shape} against a ground truth of {tuple(glab.shape)}")
+            if self.boundary is not None:                             # the boxes are needed twice: computed here, once
+                pred_stats = label_stats(plab, n_pred) if pred_stats is None else pred_stats
+                gt_stats = label_stats(glab, n_gt) if gt_stats is None else gt_stats
             c = contingency(plab, glab, n_pred, n_gt, pred_stats, gt_stats)
+            if self.boundary is not None:
+                self._add_boundary(plab, glab, c, pred_stats, gt_stats, True)
         else:
             glab, n_gt = self._host_gt(gt)
             if tuple(glab.shape) != shape:
                 raise KGLibraryError(f"LabelEvaluator.add: a predicted map of {shape} against a ground truth of {tuple(glab.shape)}")
             c = contingency_host(plab, glab, n_pred, n_gt)
+            if self.boundary is not None:
+                self._add_boundary(plab, glab, c, label_stats_host(plab, n_pred), label_stats_host(glab, n_gt), False)
         self.add_contingency(c, conf)
         return c
 
@@ -417,26 +456,34 @@ class LabelEvaluator:
     def summary(self):
         """thresholds; seg_ap, seg_iou per threshold (as Evaluator.summary; npos is the number of GT ids with non-zero area); kaggle = the
         mean of the image scores; pq, sq, dq from the summed tp, fp, fn, sum_iou; aji = the mean over images of C / U (images with U == 0
-        skipped); dice from the summed numerators and denominators; images.  A part nothing was added to is None."""
+        skipped); dice from the summed numerators and denominators; images.  A part nothing was added to is None.  With boundary= set:
+        hd, hd95, assd, nsd = the means over all true-positive pairs added (math.fsum, so no order matters; inf when a pair has an
+        unreachable side) and boundary_pairs, their number."""
         nt = len(self.thresholds)
         seg = self.seg.scores or self.seg.npos
         tp, fp, fn, s = self.pq["tp"], self.pq["fp"], self.pq["fn"], self.pq["sum_iou"]
         den = tp + 0.5 * fp + 0.5 * fn
-        return {"thresholds": self.thresholds,
-                "seg_ap": np.array([self.seg.ap(t, self.use_07_metric) for t in range(nt)]) if seg else None,
-                "seg_iou": np.array([np.mean(self.seg.overlaps[t]) for t in range(nt)]) if seg else None,
-                "kaggle": float(np.mean(self.scores)) if self.scores else None,
-                "pq": s / den if den else None, "sq": (s / tp if tp else 0.0) if den else None, "dq": tp / den if den else None,
-                "aji": float(np.mean(self.aji)) if self.aji else None,
-                "dice": self.dice[0] / self.dice[1] if self.dice[1] else None,
-                "images": self.images}
+        out = {"thresholds": self.thresholds,
+               "seg_ap": np.array([self.seg.ap(t, self.use_07_metric) for t in range(nt)]) if seg else None,
+               "seg_iou": np.array([np.mean(self.seg.overlaps[t]) for t in range(nt)]) if seg else None,
+               "kaggle": float(np.mean(self.scores)) if self.scores else None,
+               "pq": s / den if den else None, "sq": (s / tp if tp else 0.0) if den else None, "dq": tp / den if den else None,
+               "aji": float(np.mean(self.aji)) if self.aji else None,
+               "dice": self.dice[0] / self.dice[1] if self.dice[1] else None,
+               "images": self.images}
+        if self.boundary is not None:
+            for key, v in self.distances.items():
+                out[key] = math.fsum(v) / len(v) if v else None
+            out["boundary_pairs"] = len(self.distances["hd"])
+        return out
 
 
-def evaluate_tiled(model, samples, tile=(512, 512), overlap=128, **predict_tiled_kwargs):
+def evaluate_tiled(model, samples, tile=(512, 512), overlap=128, boundary=None, **predict_tiled_kwargs):
     """samples yields (image, gt): image as predict_tiled takes it (uint8 [H, W, 3]), gt as LabelEvaluator.add takes it, at the image's
-    size.  Per sample: tiling.predict_tiled, then LabelEvaluator.add on its result.  Returns LabelEvaluator.summary()."""
+    size.  Per sample: tiling.predict_tiled, then LabelEvaluator.add on its result.  boundary: LabelEvaluator's.  Returns
+    LabelEvaluator.summary()."""
     from . import tiling
-    ev = LabelEvaluator()
+    ev = LabelEvaluator(boundary=boundary)
     for image, gt in samples:
         ev.add(tiling.predict_tiled(model, image, tile=tile, overlap=overlap, **predict_tiled_kwargs), gt)
     return ev.summary()
