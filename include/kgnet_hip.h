@@ -925,6 +925,43 @@ int kg_label_thin(const int* labels, int nimg, int H, int W, const int* jobs, in
 #define KG_BORDER_MAX_TARGET_PIXELS 8192
 int kg_label_border_counts(const int* a, const int* b, int nimg, int H, int W, const int* jobs, int m, int mode, int* counts, void* stream);
 int kg_label_border_d2(const int* a, const int* b, int nimg, int H, int W, const int* jobs, int m, int mode, int* d2, int D, void* stream);
+/* Instance crops (csrc/crops.hip; crops.py states the semantics in NumPy as crops_host): one fixed-size image patch and one mask per job, the
+ * instance itself in the form a second network takes.  A gather with integer arithmetic: everything is exact in integers.
+ * JOB.  int32 [10] = {img, id, oy, ox, ay, by, cy, ax, bx, cx}.  Output pixel (i, j), 0 <= i < OH, 0 <= j < OW, samples the source position,
+ * in units of 1/65536 pixel with pixel centres at integers,
+ *   Y = (oy << 16) + ay * i + by * j + cy        X = (ox << 16) + ax * i + bx * j + cx        (int64)
+ * The kernel knows nothing of windows or angles: crops.affine_jobs builds the table (align_corners=False windows, rotations, flips).
+ * MASK.  yn = (Y + 32768) >> 16, xn = (X + 32768) >> 16 with arithmetic shifts.  mask = 1 iff 0 <= yn < H, 0 <= xn < W and
+ * labels[img][yn][xn] == id, otherwise 0.  Labels are compared only: 0, -1, INT_MIN and INT_MAX are ordinary ids.
+ * PATCH, LINEAR (flags bit 0 clear).  y0 = Y >> 16, fy = Y & 65535; x0, fx likewise.  A tap (y, x) inside the map is the image element
+ * of the channel, read unsigned; a tap outside is `fill`.  acc = (65536 - fy) * ((65536 - fx) * v00 + fx * v01) + fy * ((65536 - fx) * v10
+ * + fx * v11) with v00 = (y0, x0), v01 = (y0, x0 + 1), v10 = (y0 + 1, x0), v11 = (y0 + 1, x0 + 1); the value is (acc + 2^31) >> 32.
+ * acc < 2^48, so unsigned 64-bit arithmetic holds it for 2-byte elements.
+ * PATCH, NEAREST (flags bit 0 = KG_CROPS_NEAREST).  The tap at (yn, xn), or fill.
+ * MASKED (flags bit 1 = KG_CROPS_MASKED).  After sampling, a pixel whose mask is 0 becomes fill.
+ * OUTPUTS.  patches = device [m][channels][OH][OW] of the image's element type (channel-first), masks = device uint8 [m][OH][OW].  Either
+ * may be absent: a NULL image (with NULL patches) gives masks only, NULL masks gives patches only; at least one is required.  1 <= OH, OW <=
+ * 256; 0 <= fill <= 65535, and <= 255 when 1-byte patches are written; m * channels * OH * OW <= 2^31 - 1 (m * OH * OW without patches).
+ * image = device [nimg][H][W][channels] of unsigned elements of elem_bytes bytes (1 or 2), 1 <= channels <= 4; H, W <= 32768 and
+ * nimg * H * W <= 2^31 - 1 as for kg_label_measure.
+ * BAD JOBS.  A job whose img lies outside [0, nimg) gets fill and a zero mask.  No other job is bad: a window that lies beyond the map is
+ * padding, not an error.  Every output element is written.
+ * Consequences, pinned by the host statement: ay = bx = 65536 with the other coefficients 0 copies the slice; ay = bx = 131072, cy = cx =
+ * 32768 gives the mean of each 2 x 2 block rounded half up; an image of 65535 stays 65535 under any fractions; {ay, by, ax, bx} =
+ * {0, -65536, 65536, 0} gives the patch and the mask turned by 90 degrees.
+ * INDEX RULE.  The first kind of exception, the caller's job table: img is used inside (unsigned)img < (unsigned)nimg, and every tap inside
+ * the unsigned 64-bit predicates (unsigned long long)y < H, (unsigned long long)x < W, formed from the int64 Y, X before any narrowing, so
+ * extreme coefficients and far origins give fill and cannot leave the buffers.  No address depends on a label or a pixel value.  No
+ * atomics, no LDS, no synchronisation.
+ * ONE launch whatever m is: a work item is (job, chunk of 1024 output positions in raster order), the grid is capped at 2^20 workgroups of
+ * 256 that stride over what is left; a thread owns 4 consecutive positions and stores them as 32-bit words where the plane offset is
+ * aligned.  m == 0 launches nothing (jobs and the outputs may then be NULL).  Validates on the host before any HIP call (null pointers, nimg,
+ * H, W > 0, the size rules, channels, elem_bytes, the output size, flags, fill, m >= 0, alignment, the outputs overlapping neither an input
+ * nor each other) and never synchronises. */
+#define KG_CROPS_NEAREST 1
+#define KG_CROPS_MASKED 2
+int kg_label_crops(const int* labels, int nimg, int H, int W, const void* image, int channels, int elem_bytes, const int* jobs, int m, int OH,
+                   int OW, int flags, int fill, void* patches, unsigned char* masks, void* stream);
 
 /* ---- per-box segmentation branch (KGnet.py:246-267, 321-350): ragged row bookkeeping ---- */
 int kg_seg_build_rows(const int* boxtab8, int nb, int* rowdesc, int* row2box, int* srcrow, void* stream);

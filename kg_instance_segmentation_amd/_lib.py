@@ -129,6 +129,7 @@ _SIGS = {
     "kg_label_thin": [P, c_int, c_int, c_int, P, c_int, c_int, P, P, P],
     "kg_label_border_counts": [P, P, c_int, c_int, c_int, P, c_int, c_int, P, P],
     "kg_label_border_d2": [P, P, c_int, c_int, c_int, P, c_int, c_int, P, c_int, P],
+    "kg_label_crops": [P, c_int, c_int, c_int, P, c_int, c_int, P, c_int, c_int, c_int, c_int, c_int, P, P, P],
     "kg_f64_probe": [P, P, P, c_int, P],
     "kg_seg_build_rows": [P, c_int, P, P, P, P],
     "kg_seg_build_rows_levels": [c_int, P, P, P, P, P, P],

@@ -57,6 +57,7 @@ SOURCES = {
     "texture.hip": [],
     "thinning.hip": [],
     "boundaries.hip": [],
+    "crops.hip": [],
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function"]

@@ -112,7 +112,7 @@ def instances_from_predictions(preds):
 
 
 def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None, max_workspace_bytes=None, clean=None, measure=None,
-                      expand=None, neighbours=None, runs=None, contours=None, hulls=None, quantiles=None, split=None, texture=None, thin=None):
+                      expand=None, neighbours=None, runs=None, contours=None, hulls=None, quantiles=None, split=None, texture=None, thin=None, crops=None):
     """predict(packed=True) followed by the instance label map and the per-instance table of every image (instances.py), on the device:
     the label map (4 bytes per pixel) and the table (64 bytes per instance) replace n full-size masks as what crosses to the host.
     clean: None, or a dict of components.clean's policy arguments: every label map is then cleaned on the device (one components pass
@@ -151,7 +151,12 @@ def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None
     thin: None; True, or a dict of thinning.thin_instances_batch's keyword arguments (max_passes): every result's `midlines` holds the
     midline of its instances (thinning.py: length, tips, branch points, and the midline map `skel`), taken next to the other
     measurements on the final label map -- one upload, one launch and one copy back for all images of one output size.  None adds no
-    launch and no import."""
+    launch and no import.
+    crops: None; a uint8 / uint16 [N, h, w, C] array or device tensor at the label maps' size, or a dict {"image": that (None: masks only),
+    "size": ..., "window": ..., "margin": ..., "angle": ..., "side": ..., "flip": ..., "mode": ..., "masked": ..., "fill": ..., "masks": ...}
+    of crops.crops_instances_batch's arguments: every result's `crops` holds one fixed-size patch and mask per instance, on the device
+    (crops.py: what a second network takes), taken last, next to hulls, on the final label map -- one upload (the table) and one launch
+    for all images of one output size, nothing copied back.  None adds no launch and no import."""
     if not torch.is_tensor(x) or x.device.type != "cuda":
         raise _lib.KGLibraryError("predict_instances (MI355X build) needs the input batch on a GPU device")
     out = instances_from_predictions(predict(model, x, nms_thresh, seg_thresh, image_sizes, max_workspace_bytes=max_workspace_bytes, packed=True))
@@ -190,6 +195,10 @@ def predict_instances(model, x, nms_thresh=0.5, seg_thresh=0.5, image_sizes=None
     if hulls is not None and hulls is not False:
         from . import hulls as _hulls
         _hulls.hulls_instances_batch(out, **({} if hulls is True else dict(hulls)))
+    if crops is not None and crops is not False:
+        from . import crops as _crops
+        kw = dict(crops) if isinstance(crops, dict) else {"image": crops}
+        _crops.crops_instances_batch(out, kw.pop("image", None), **kw)
     return out
 
 

@@ -31,9 +31,9 @@ class Instances:
     neighbours = None unless asked for (neighbours=, neighbours.py: a Neighbours); runs = None unless asked for (runs=, runlengths.py: a
     RunLengths); contours = None unless asked for (contours=, contours.py: a Contours); hulls = None unless asked for (hulls=, hulls.py: a
     Hulls); quantiles = None unless asked for (quantiles=, intensity.py: a Quantiles); texture = None unless asked for (texture=, texture.py:
-    a CoMatrices); midlines = None unless asked for (thin=, thinning.py: a Midlines, which keeps the midline map `skel`); parent = None unless a split ran (split=, split.py): then int32 [n], and dets holds a copy of the parent's row for every new id while masks keeps the rows of the parents only:
+    a CoMatrices); midlines = None unless asked for (thin=, thinning.py: a Midlines, which keeps the midline map `skel`); crops = None unless asked for (crops=, crops.py: a Crops, patches and masks on the device); parent = None unless a split ran (split=, split.py): then int32 [n], and dets holds a copy of the parent's row for every new id while masks keeps the rows of the parents only:
     masks[parent[i]] is the mask instance i + 1 came from (parent[i] == i for an instance that was there before the split)."""
-    __slots__ = ("labels", "dets", "table", "masks", "measurements", "neighbours", "runs", "contours", "hulls", "quantiles", "texture", "midlines", "parent")
+    __slots__ = ("labels", "dets", "table", "masks", "measurements", "neighbours", "runs", "contours", "hulls", "quantiles", "texture", "midlines", "crops", "parent")
 
     def __init__(self, labels, dets, table, masks):
         self.labels, self.dets, self.table, self.masks = labels, dets, table, masks
@@ -45,6 +45,7 @@ class Instances:
         self.quantiles = None
         self.texture = None
         self.midlines = None
+        self.crops = None
         self.parent = None
 
     def __len__(self):

@@ -217,7 +217,7 @@ class TiledInstances(Instances):
     """predict_tiled's result: labels = device int32 [H, W] (assemble_host: a NumPy array); dets = float32 [n, 5] (y1, x1, y2, x2, conf) in
     global pixels, clipped to the image, in id order; table = host int64 [n, 8]; masks = None; tile int32 [n]; origin int32 [n, 2];
     tile_masks = the tile-local mask rows in id order (BitMasks; assemble_host: uint8 [n, th, tw]): tile_masks[i] placed at origin[i]
-    is the full mask of instance i + 1.  measurements, neighbours, runs, contours, hulls, quantiles, texture and midlines are Instances': None unless
+    is the full mask of instance i + 1.  measurements, neighbours, runs, contours, hulls, quantiles, texture, midlines and crops are Instances': None unless
     asked for (measure=, neighbours=, runs=, contours=, hulls=, quantiles=, texture=, thin= of predict_tiled).  parent is Instances' too: None unless a split ran
     (split=, split.py); then dets, tile and origin hold a copy of the parent's row for every new id and tile_masks keeps the rows of the
     parents only: tile_masks[parent[i]] placed at origin[i] is the mask instance i + 1 came from."""
@@ -487,7 +487,7 @@ def assemble(plan, per_tile_preds, nms_thresh=0.5, device=None, stage=None, clea
 
 
 def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thresh=0.5, seg_thresh=0.5, max_workspace_bytes=None, stage=None,
-                  clean=None, measure=False, expand=None, neighbours=None, runs=None, contours=None, hulls=None, quantiles=None, split=None, texture=None, thin=None):
+                  clean=None, measure=False, expand=None, neighbours=None, runs=None, contours=None, hulls=None, quantiles=None, split=None, texture=None, thin=None, crops=None):
     """Instance segmentation of a whole image at native resolution -> TiledInstances.  image: host uint8 [H, W, 3] (uploaded once, to the
     model's device) or a device uint8 tensor; tile: the network input size, (th, tw) or one int, multiples of 32; overlap: pixels two
     neighbouring tiles share at least (choose it at least as large as the largest object: an object is cut at the edge of the tile that
@@ -523,11 +523,18 @@ def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thres
     thin: None; True, or a dict of thinning.thin_instances' keyword arguments (max_passes): the result's `midlines` then holds the midline
     of the instances of the STITCHED map (thinning.py: length, tips, branch points, and the midline map `skel`; no tile seams), taken
     next to the other measurements on the final label map -- one more upload, launch and copy back.  None adds no launch and no
-    import."""
+    import;
+    crops: None; True (patches of the uploaded uint8 image), another uint8 / uint16 [H, W, C] image, or a dict of crops.crops_instances'
+    keyword arguments (size, window, margin, angle, side, flip, mode, masked, fill, masks; "image": another image, None for masks only):
+    the result's `crops` then holds one fixed-size patch and mask per instance, on the device (crops.py: what a second network takes),
+    taken last, next to hulls, on the final label map -- one more upload (the table) and launch, nothing copied back.  None adds no launch
+    and no import."""
     import torch
     from . import inference
     quantiles = None if quantiles is False else quantiles
     texture = None if texture is False else texture
+    crops = None if crops is False else crops
+    crops_own = crops is True or (isinstance(crops, dict) and "image" not in crops)     # crops of the uploaded image
     if int(batch) < 1:
         raise KGLibraryError(f"predict_tiled: batch {batch}")
     mark = stage if stage is not None else (lambda name: None)
@@ -535,7 +542,7 @@ def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thres
         shape, dev = tuple(image.shape), image.device
     else:
         shape, dev = _host_image(image).shape, next(model.parameters()).device
-        if measure or quantiles is not None or texture is not None:   # the one upload serves the tiles and the measurements
+        if measure or quantiles is not None or texture is not None or crops_own:   # the one upload serves the tiles and the measurements
             from . import ops
             image = ops.h2d(_host_image(image), dev)
     if len(shape) != 3 or shape[2] != 3:
@@ -576,4 +583,8 @@ def predict_tiled(model, image, tile=(512, 512), overlap=128, batch=8, nms_thres
     if hulls is not None and hulls is not False:
         from . import hulls as _hulls
         out.hulls = _hulls.hulls_instances(out, **({} if hulls is True else dict(hulls)))
+    if crops is not None:
+        from . import crops as _crops
+        kw = dict(crops) if isinstance(crops, dict) else {} if crops is True else {"image": crops}
+        out.crops = _crops.crops_instances(out, kw.pop("image", image), **kw)
     return out
