@@ -311,11 +311,28 @@ int kg_gt_maps(const float* kps, int n, int H, int W, float* out, void* stream);
  * kg_sp_boxes: box -> per image, in instance order: kp = device float32 [4][ntot][5][2], the keypoints (x, y) of tl, tr, bl, br, centre
  *   of the instances kept at each scale (dataset_base.py:72-78); gtb = device float32 [ntot][5] = (y1, x1, y2, x2, 1) and keep = device
  *   int32 [ntot] (instance index) of the instances load_gt_masks_bboxes keeps (dataset_base.py:43-56); the lists of image i start at row
- *   inst0 of their table; counts = device int32 [N][5] (scales 1, 2, 4, 8, gt). ---- */
+ *   inst0 of their table; counts = device int32 [N][5] (scales 1, 2, 4, 8, gt).
+ * Ground truth as a label map: with flag 8 (SP_LABELS) masks = int32 [h][w], the label map of the image, and ld is ignored; kg_sp_image
+ *   and kg_sp_boxes ignore the flag, and such a record is never passed to kg_sp_warp_masks.
+ * kg_sp_warp_labels: kg_sp_warp_masks for label-map images.  jobs = device int32 [ntot][6] = (img, id, y1, x1, y2, x2), the half-open
+ *   box in source coordinates, rows inst0 .. inst0 + n - 1 those of image img; out = device bytes [ntot][H][W] of 0 / 1; box as above,
+ *   zero-filled by the caller, in the same encoding.  With (sy, sx) the source index of output pixel (y, x) under the record of image img
+ *   (the composite map above: -1 outside the paste window), pixel (y, x) of job k is 1 iff all of: (unsigned)img < (unsigned)N; sy and sx
+ *   lie inside the paste window; (sy, sx) lies inside the job box clamped to [0, h] x [0, w]; labels[sy][sx] == id.  Otherwise it is 0:
+ *   a pixel outside the window is 0 whatever id is, id = 0 included.  id is any int32 and is compared only; img and the box are
+ *   predicates only, no address is formed from them nor from a label, so a wrong table gives zeros or wrong pixels and cannot leave the
+ *   buffers; the source is loaded only inside the forward image of the box.  A record without flag 8 gives zeros.  One launch; every
+ *   output element is written.  Refused before any launch: null pointers (ntot == 0 returns 0 with null buffers), N outside 1 .. 65535,
+ *   ntot < 0, H or W no multiple of 8, H > 65535, W > 4096, jobs / box off 4-byte alignment (out off 16-byte alignment when W % 16 == 0),
+ *   out, box and jobs overlapping.
+ * kg_sp_warp_labelmap: out = device int32 [N][H][W], out[i][y][x] = labels_i[sy][sx] inside the paste window and 0 outside.  One
+ *   launch.  For every job whose box holds all pixels of its id, kg_sp_warp_labels' out[k] == (out[img] == id). ---- */
 int kg_sp_image(const void* imgs, int N, int H, int W, float* out, void* stream);
 int kg_sp_warp_masks(const void* imgs, const int* inst_img, int ntot, int H, int W, void* out, int* box, void* stream);
 int kg_sp_boxes(const void* imgs, int N, const int* box, int ntot, int kp_radius, int* counts, float* gtb, float* kp, int* keep,
                 void* stream);
+int kg_sp_warp_labels(const void* imgs, int N, const int* jobs, int ntot, int H, int W, void* out, int* box, void* stream);
+int kg_sp_warp_labelmap(const void* imgs, int N, int H, int W, int* out, void* stream);
 
 /* ---- fused multi-tensor Adam step (train.py:71,154), fp32, torch.optim.Adam's operation order.  jobs = device array of 48-byte
  * records {float* p; const float* g; float* m; float* v; long n; int blk0; int pad;}, blk0 = first workgroup of the job (4096

@@ -85,6 +85,8 @@ _SIGS = {
     "kg_sp_image": [P, c_int, c_int, c_int, P, P],
     "kg_sp_warp_masks": [P, P, c_int, c_int, c_int, P, P, P],
     "kg_sp_boxes": [P, c_int, P, c_int, c_int, P, P, P, P, P],
+    "kg_sp_warp_labels": [P, c_int, P, c_int, c_int, c_int, P, P, P],
+    "kg_sp_warp_labelmap": [P, c_int, c_int, c_int, P, P],
     "kg_adam_step": [P, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_float, P],
     "kg_host_crop_masks": [P, P, c_int, c_int, c_int, P],
     "kg_crop_masks": [P, P, c_int, c_int, c_int, P, P],

@@ -1,6 +1,7 @@
 // label_common.h -- what the label-map kernels share (instances.hip, tiling.hip, labelmetrics.hip, components.hip, measure.hip,
 // distance.hip, neighbours.hip, runlengths.hip, contours.hip, polygons.hip, hulls.hip, intensity.hip, split.hip, texture.hip,
-// thinning.hip, boundaries.hip, crops.hip; paste.hip for the bit-mask leading dimension): wave reductions, the clamped job box and its walk, the block combine of four wave partials, the
+// thinning.hip, boundaries.hip, crops.hip; paste.hip for the bit-mask leading dimension; sampleprep.hip for the job box and the host
+// checks of kg_sp_warp_labels): wave reductions, the clamped job box and its walk, the block combine of four wave partials, the
 // row-segment run walk, per-image ranges passed by value, and the host argument checks -- among them the side bound KG_LABEL_MAX_SIDE,
 // the block that opens a per-job entry (kg_check_job_stack), the image check (kg_check_image) and the overlap test (kg_apart).
 // Integers only, plain C++ and vector memory operations only.
@@ -13,7 +14,9 @@
 //     cannot make a kernel leave its buffers.  kg_label_crops (crops.hip) is of this kind without a box: the sampling positions of its
 //     job table are int64 sums of the table's coefficients, img is used inside (unsigned)img < (unsigned)nimg, and every tap (y, x) only
 //     inside the unsigned 64-bit predicates (unsigned long long)y < H and (unsigned long long)x < W, formed BEFORE any narrowing; a tap
-//     that fails them is the fill value, so extreme coefficients and far origins cannot leave the buffers either;
+//     that fails them is the fill value, so extreme coefficients and far origins cannot leave the buffers either.  kg_sp_warp_labels
+//     (sampleprep.hip) is of this kind with the box as a predicate: img selects an image record only inside (unsigned)img < (unsigned)N,
+//     the clamped box only gates the load, and the load's address comes from the output pixel's own source index (sp_src);
 //   - a row a label selects (kg_label_stats, kg_component_stats / remap, the union-find parents): stated in labelmetrics.hip and
 //     components.hip, the index is formed only inside (unsigned)(v - 1) < (unsigned)n;
 //   - the run slot of kg_label_runs (runlengths.hip): an offset of the job table plus a prefix count of predicates -- not a label value --

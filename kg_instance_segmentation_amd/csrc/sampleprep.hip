@@ -11,13 +11,24 @@
 // The image goes through the same map per bilinear tap (transforms.py:170, float32 INTER_LINEAR as lin_taps.h / oracle/paste.py state
 // it), after the photometric arithmetic (transforms.py:32,45: two float32 operations) and before dataset_base.py:104-106.
 // Compiled with -ffp-contract=off: every float product and sum rounds as written.
+//
+// Ground truth may also arrive as ONE int32 label map per image (flag SP_LABELS) with a job table (img, id, y1, x1, y2, x2) in place of
+// one plane per instance: kg_sp_warp_labels warps `labels == id` through the same source index, kg_sp_warp_labelmap the map itself.
+// The index rule of label_common.h holds there, with its first exception, the caller's job table: img and the box are PREDICATES only.
+// img selects an image record only inside (unsigned)img < (unsigned)N, the box is clamped to the map (kg_job_box) and only gates the
+// load, and the address of the load is formed from the output pixel's own source index (sp_src: inside [0, h) x [0, w) or -1), never
+// from the table and never from a label: id and the labels are compared only.  A hostile table gives zeros or wrong pixels and cannot
+// leave the buffers.  The source is loaded only where the row and the column predicate hold, so an output pixel outside the forward
+// image of the box costs a store and no load.
 #include "kg_common.h"
+#include "label_common.h"
 #include "lin_taps.h"
 
 #define SP_MAXW 4096            // widest output row (the column map of a row lives in LDS)
 #define SP_MIRROR_W 1
 #define SP_MIRROR_H 2
 #define SP_BITS 4
+#define SP_LABELS 8             // masks = int32 [h][w], the label map of the image (kg_sp_warp_labels, kg_sp_warp_labelmap); ld is ignored
 
 // one image of the batch (80 bytes; sampleprep.py builds the table with the same layout)
 struct SpImage {
@@ -194,6 +205,157 @@ extern "C" int kg_sp_warp_masks(const void* imgs, const int* inst_img, int ntot,
         hipLaunchKernelGGL(sp_warp_kernel<4>, dim3((unsigned)kg_cdiv((long)H * (W / 4), 256), gy), dim3(256), 0, (hipStream_t)stream,
                            (const SpImage*)imgs, inst_img, ntot, H, W, (unsigned char*)out, box);
     KG_CHECK_LAUNCH("sp_warp_masks");
+    return KG_OK;
+}
+
+// ---- label maps -------------------------------------------------------------------------------------------------------------------
+// The mask kernel's lane: PX bits of one output row -> ONE dword (PX 4) or dwordx4 (PX 16) of 0 / 1 bytes
+template <int PX>
+__device__ __forceinline__ void sp_store_bits(unsigned char* o, unsigned m) {
+    if (PX == 16) {
+        uint4 v;
+        v.x = ((m & 15u) * 0x00204081u) & 0x01010101u;
+        v.y = (((m >> 4) & 15u) * 0x00204081u) & 0x01010101u;
+        v.z = (((m >> 8) & 15u) * 0x00204081u) & 0x01010101u;
+        v.w = (((m >> 12) & 15u) * 0x00204081u) & 0x01010101u;
+        *reinterpret_cast<uint4*>(o) = v;
+    } else {
+        *reinterpret_cast<unsigned*>(o) = ((m & 15u) * 0x00204081u) & 0x01010101u;
+    }
+}
+// ... and its fold of the lane's ones (m != 0) into the workgroup's LDS box at the four divide scales, in kg_sp_warp_masks' encoding
+template <int PX>
+__device__ __forceinline__ void sp_fold_bits(int* sbox, unsigned m, int y, int x0) {
+#pragma unroll
+    for (int l = 0; l < 4; ++l) {
+        if (y & ((1 << l) - 1)) continue;
+        const unsigned pat = l == 0 ? 0xffffu : l == 1 ? 0x5555u : l == 2 ? 0x1111u : ((x0 & 7) ? 0u : 0x0101u);
+        const unsigned mm = m & pat & ((1u << PX) - 1u);
+        if (!mm) continue;
+        const int lo = (x0 + __builtin_ctz(mm)) >> l, hi = (x0 + 31 - __builtin_clz(mm)) >> l, ys = y >> l;
+        atomicMax(&sbox[4 * l + 0], 0x10000 - ys);
+        atomicMax(&sbox[4 * l + 1], 0x10000 - lo);
+        atomicMax(&sbox[4 * l + 2], ys + 1);
+        atomicMax(&sbox[4 * l + 3], hi + 1);
+    }
+}
+
+// The mask kernel's shape (a workgroup = one job x 256 pixel groups, a lane = PX adjacent pixels of one output row), reading
+// labels[sy][sx] == id in place of a mask plane.  Output pixel (y, x) of job k is 1 iff (unsigned)img < (unsigned)N, sy and sx lie inside
+// the paste window, (sy, sx) lies inside the job box clamped to [0, h] x [0, w], and labels[sy][sx] == id; otherwise 0.
+// The box makes most of the output a plain fill: a lane loads only when its row lies in the box's rows, and there only the pixels whose
+// column lies in the box's columns.  A workgroup none of whose rows meets the box (a workgroup-uniform vote) stores its zeros and skips
+// the column map, the fold and the atomics.  (A workgroup visits a second job only beyond 65 535 jobs, so keeping the column map between
+// the jobs of one image would save nothing at any measured size: it is rebuilt per job, as in the mask kernel.)
+template <int PX>
+__global__ __launch_bounds__(256) void sp_warp_labels_kernel(const SpImage* __restrict__ imgs, int N, const int* __restrict__ jobs, int ntot, int H, int W,
+                                                             unsigned char* __restrict__ out, int* __restrict__ box) {
+    __shared__ int xmap[SP_MAXW];
+    __shared__ int sbox[16];
+    const int gpr = W / PX, ngroups = H * gpr;
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    const int y = g / gpr, x0 = (g - y * gpr) * PX;
+    for (int k = blockIdx.y; k < ntot; k += gridDim.y) {
+        const int* jb = jobs + (long)k * 6;
+        const int img = jb[0], id = jb[1];
+        const bool live = (unsigned)img < (unsigned)N;                               // the only place img may become an index
+        const int ii = live ? img : 0;
+        const SpImage im = imgs[ii];
+        const KgBox b = kg_job_box(jb + 2, im.h, im.w);
+        const bool open = live && (im.flags & SP_LABELS) && im.masks != nullptr;     // (a record that is no label map gives zeros)
+        int sy = -1;
+        if (open && g < ngroups) {
+            sy = sp_src(y, im.h, im.He, im.oy, im.flags & SP_MIRROR_H, H);
+            if ((unsigned)(sy - b.y1) >= (unsigned)b.h) sy = -1;                     // outside the window (-1) or outside the box's rows
+        }
+        // (also the barrier between the previous job's reads of xmap / sbox and the writes below)
+        const int any = __syncthreads_or(sy >= 0 && b.w > 0);
+        unsigned m = 0;
+        if (any) {
+            for (int x = threadIdx.x; x < W; x += 256) xmap[x] = sp_src(x, im.w, im.We, im.ox, im.flags & SP_MIRROR_W, W);
+            if (threadIdx.x < 16) sbox[threadIdx.x] = 0;
+            __syncthreads();
+            if (sy >= 0) {
+                const int* row = (const int*)im.masks + (long)sy * im.w;
+#pragma unroll
+                for (int e = 0; e < PX; ++e) {
+                    const int sx = xmap[x0 + e];
+                    if ((unsigned)(sx - b.x1) < (unsigned)b.w && row[sx] == id) m |= 1u << e;    // sx = -1 fails: b.x1 >= 0
+                }
+            }
+        }
+        if (g < ngroups) sp_store_bits<PX>(out + (long)k * H * W + (long)y * W + x0, m);
+        if (any) {
+            if (m) sp_fold_bits<PX>(sbox, m, y, x0);
+            __syncthreads();
+            if (threadIdx.x < 16 && sbox[threadIdx.x]) atomicMax(&box[(long)k * 16 + threadIdx.x], sbox[threadIdx.x]);
+        }
+    }
+}
+
+// imgs: device SpImage [N], label-map images (SP_LABELS: masks = int32 [h][w]); jobs: device int32 [ntot][6] = (img, id, y1, x1, y2, x2),
+// the box half-open in source coordinates, rows inst0 .. inst0 + n - 1 those of image img; out: device bytes [ntot][H][W] of 0 / 1;
+// box: device int32 [ntot][16], ZERO-FILLED by the caller, kg_sp_warp_masks' encoding.  One launch; every output element is written.
+// Every index is a long: ntot * H * W < 2^31 * 2^16 * 2^12 and ntot * 16 fit it whatever the arguments.
+extern "C" int kg_sp_warp_labels(const void* imgs, int N, const int* jobs, int ntot, int H, int W, void* out, int* box, void* stream) {
+    const char* fn = "kg_sp_warp_labels";
+    KG_CHECK_ARG(N >= 1 && N <= 65535, "%s: N %d (1 .. 65535)", fn, N);
+    KG_CHECK_ARG(ntot >= 0, "%s: bad size (ntot %d)", fn, ntot);
+    KG_CHECK_ARG(H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0 && H <= 65535 && W <= SP_MAXW, "%s: output %d x %d must be multiples of 8, H <= 65535, W <= %d", fn,
+                 H, W, SP_MAXW);
+    KG_CHECK_ARG((long)ntot <= LONG_MAX / ((long)H * W) && (long)ntot <= LONG_MAX / 64, "%s: ntot * H * W exceeds the index type", fn);
+    if (ntot == 0) return KG_OK;
+    KG_CHECK_ARG(imgs && jobs && out && box, "%s: null pointer", fn);
+    const long obytes = (long)ntot * H * W, bbytes = (long)ntot * 64, jbytes = (long)ntot * 24;
+    KG_CHECK_ARG(kg_aligned(imgs, 7) && kg_aligned(jobs, 3) && kg_aligned(box, 3) && kg_aligned(out, W % 16 == 0 ? 15 : 3), "%s: misaligned pointer", fn);
+    KG_CHECK_ARG(kg_apart(out, obytes, box, bbytes) && kg_apart(out, obytes, jobs, jbytes) && kg_apart(box, bbytes, jobs, jbytes) &&
+                     kg_apart(out, obytes, imgs, (long)N * 80) && kg_apart(box, bbytes, imgs, (long)N * 80),
+                 "%s: an output overlaps an input or the other output", fn);
+    const unsigned gy = (unsigned)(ntot < 65535 ? ntot : 65535);
+    if (W % 16 == 0)
+        hipLaunchKernelGGL(sp_warp_labels_kernel<16>, dim3((unsigned)kg_cdiv((long)H * (W / 16), 256), gy), dim3(256), 0, (hipStream_t)stream,
+                           (const SpImage*)imgs, N, jobs, ntot, H, W, (unsigned char*)out, box);
+    else
+        hipLaunchKernelGGL(sp_warp_labels_kernel<4>, dim3((unsigned)kg_cdiv((long)H * (W / 4), 256), gy), dim3(256), 0, (hipStream_t)stream,
+                           (const SpImage*)imgs, N, jobs, ntot, H, W, (unsigned char*)out, box);
+    KG_CHECK_LAUNCH("sp_warp_labels");
+    return KG_OK;
+}
+
+// out[i][y][x] = labels_i[sy][sx] inside the paste window, 0 outside (and 0 for a record that is no label map).  One lane: 4 adjacent
+// pixels of one row, one 16-byte store.  The labels are stored values only; every address comes from sp_src.
+__global__ __launch_bounds__(256) void sp_warp_labelmap_kernel(const SpImage* __restrict__ imgs, int H, int W, int* __restrict__ out) {
+    const int q = blockIdx.x * 256 + threadIdx.x, qpr = W >> 2;
+    if (q >= H * qpr) return;
+    const int y = q / qpr, x0 = (q - y * qpr) << 2;
+    const SpImage im = imgs[blockIdx.y];
+    int v[4] = {0, 0, 0, 0};
+    if ((im.flags & SP_LABELS) && im.masks != nullptr) {
+        const int sy = sp_src(y, im.h, im.He, im.oy, im.flags & SP_MIRROR_H, H);
+        if (sy >= 0) {
+            const int* row = (const int*)im.masks + (long)sy * im.w;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int sx = sp_src(x0 + e, im.w, im.We, im.ox, im.flags & SP_MIRROR_W, W);
+                if (sx >= 0) v[e] = row[sx];
+            }
+        }
+    }
+    *reinterpret_cast<int4*>(out + ((long)blockIdx.y * H + y) * W + x0) = make_int4(v[0], v[1], v[2], v[3]);
+}
+
+// imgs: device SpImage [N], label-map images; out: device int32 [N][H][W], the nearest resize of the expanded, mirrored label maps.
+extern "C" int kg_sp_warp_labelmap(const void* imgs, int N, int H, int W, int* out, void* stream) {
+    const char* fn = "kg_sp_warp_labelmap";
+    KG_CHECK_ARG(N >= 1 && N <= 65535, "%s: N %d (1 .. 65535)", fn, N);
+    KG_CHECK_ARG(H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0 && H <= 65535 && W <= SP_MAXW, "%s: output %d x %d must be multiples of 8, H <= 65535, W <= %d", fn,
+                 H, W, SP_MAXW);
+    KG_CHECK_ARG(imgs && out, "%s: null pointer", fn);
+    KG_CHECK_ARG(kg_aligned(imgs, 7) && kg_aligned(out, 15), "%s: misaligned pointer", fn);
+    KG_CHECK_ARG(kg_apart(out, (long)N * H * W * 4, imgs, (long)N * 80), "%s: the output overlaps the image table", fn);
+    hipLaunchKernelGGL(sp_warp_labelmap_kernel, dim3((unsigned)kg_cdiv((long)H * (W >> 2), 256), (unsigned)N), dim3(256), 0, (hipStream_t)stream,
+                       (const SpImage*)imgs, H, W, out);
+    KG_CHECK_LAUNCH("sp_warp_labelmap");
     return KG_OK;
 }
 

@@ -17,6 +17,10 @@ Deviations from the reference, both on inputs it cannot process: an image with z
 (the reference raises IndexError at `masks[0]`, dataset_base.py:60); source masks are taken as foreground where non-zero (the reference
 compares the float mask with 1., dataset_base.py:47,66: identical for 0 / 1 masks).
 
+Ground truth may also be a label map (`LabelSource`: what runlengths.paint, polygons.fill and predict_instances produce): the masks
+launch is then kg_sp_warp_labels, which reads `labels == id` inside each id's box, and nothing goes through the host.  `warp_labels`
+is the warped map itself (kg_sp_warp_labelmap); `label_masks_host` / `warp_labels_host` state both in NumPy.
+
 Opt-in, like batched inference: the reference drivers and `dropin/` do not use it (INTEGRATION.md shows the loop change)."""
 from dataclasses import dataclass
 from typing import NamedTuple, Tuple
@@ -33,7 +37,7 @@ PERMS = ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0))
 DIVIDE_SCALES = (1, 2, 4, 8)            # dataset_base.py:89-92
 MAX_WIDTH = 4096                        # SP_MAXW of csrc/sampleprep.hip
 
-_MIRROR_W, _MIRROR_H, _BITS = 1, 2, 4
+_MIRROR_W, _MIRROR_H, _BITS, _LABELS = 1, 2, 4, 8
 # struct SpImage of csrc/sampleprep.hip (80 bytes)
 _REC = np.dtype([("img", "<u8"), ("masks", "<u8"), ("h", "<i4"), ("w", "<i4"), ("He", "<i4"), ("We", "<i4"), ("oy", "<i4"), ("ox", "<i4"),
                  ("flags", "<i4"), ("perm", "<i4"), ("delta", "<f4"), ("alpha", "<f4"), ("inst0", "<i4"), ("n", "<i4"), ("ld", "<i8"),
@@ -175,8 +179,129 @@ def _masks_on(m, h, w, dev):
     return wd, wd.data_ptr(), True, wd.shape[0], wd.shape[1]
 
 
+class LabelSource:
+    """The ground truth of one image as a label map instead of one mask per instance: what runlengths.paint, polygons.fill and
+    predict_instances produce.  prepare_batch takes it wherever it takes masks (a batch is all label sources or all mask sources).
+    labels: an int32 [h, w] device tensor, or a host integer array.  A host array is uploaded once, on first use, and the source keeps
+    that device copy: the array must not change afterwards (a later change is NOT seen by later batches); build a new LabelSource for a
+    changed map.  (A device tensor is read as it is at every batch.)  Give n or jobs, not both:
+      n     the instances are the ids 1 .. n, in that order.  Their boxes come from stats, [n, 5] = labelmetrics.STATS_COLUMNS as a host
+            array or as the device tensor of labelmetrics.label_stats_device; without stats they come from label_stats_device, on the
+            device.  Neither adds a device -> host copy.  A pixel value outside [0, n] belongs to no instance.
+      jobs  integers [m, 5] = (id, y1, x1, y2, x2): arbitrary ids in a chosen order, each with the half-open box that holds its pixels
+            (a smaller box cuts the instance to the box).
+    An id with no pixel keeps its row, as an all-zero mask, exactly like an all-zero plane among masks."""
+    __slots__ = ("labels", "n", "stats", "jobs", "_on")
+
+    def __init__(self, labels, n=None, stats=None, jobs=None):
+        if torch.is_tensor(labels) and labels.device.type == "cuda":
+            if labels.dtype != torch.int32 or labels.dim() != 2 or labels.numel() == 0:
+                raise ValueError("sampleprep.LabelSource: a device label map must be a non-empty int32 [h, w] tensor")
+        else:
+            a = labels.numpy() if torch.is_tensor(labels) else np.asarray(labels)
+            if a.ndim != 2 or a.dtype.kind not in "iu" or a.size == 0 or a.min() < -2 ** 31 or a.max() > 2 ** 31 - 1:
+                raise ValueError("sampleprep.LabelSource: a host label map must be a non-empty integer array [h, w] that fits int32")
+            labels = np.ascontiguousarray(a, np.int32)
+        if (n is None) == (jobs is None):
+            raise ValueError("sampleprep.LabelSource: give the instance count n or a job table, not both and not neither")
+        if jobs is not None:
+            if stats is not None:
+                raise ValueError("sampleprep.LabelSource: stats belong to n; a job table carries its own boxes")
+            j = np.asarray(jobs)
+            if j.ndim != 2 or j.shape[1] != 5 or j.dtype.kind not in "iu" or (j.size and (j.min() < -2 ** 31 or j.max() > 2 ** 31 - 1)):
+                raise ValueError("sampleprep.LabelSource: jobs must be integers [m, 5] = (id, y1, x1, y2, x2) that fit int32")
+            jobs = np.ascontiguousarray(j, np.int32)
+        else:
+            if isinstance(n, (bool, np.bool_)) or int(n) != n or not 0 <= int(n) < 2 ** 31 // 5:
+                raise ValueError(f"sampleprep.LabelSource: instance count {n!r}")
+            n = int(n)
+            if torch.is_tensor(stats):
+                if stats.dtype != torch.int32 or tuple(stats.shape) != (n, 5):
+                    raise ValueError(f"sampleprep.LabelSource: a stats tensor must be int32 [{n}, 5] = (area, y1, x1, y2, x2)")
+                if stats.device.type != "cuda":
+                    stats = stats.numpy()
+            elif stats is not None:
+                stats = np.asarray(stats)
+                if stats.shape != (n, 5) or stats.dtype.kind not in "iu" or (stats.size and (stats.min() < -2 ** 31 or stats.max() > 2 ** 31 - 1)):
+                    raise ValueError(f"sampleprep.LabelSource: stats must be integers [{n}, 5] = (area, y1, x1, y2, x2) that fit int32")
+        self.labels, self.n, self.stats, self.jobs, self._on = labels, n, stats, jobs, None
+
+    @staticmethod
+    def from_instances(inst):
+        """The label map and the table boxes of an Instances / TiledInstances (predict_instances, predict_tiled): the pseudo-label route.
+        An instance with no visible pixel gets an empty box, hence an all-zero mask."""
+        from . import _labelmaps
+        try:
+            stats = _labelmaps.instance_stats("sampleprep.LabelSource.from_instances", inst)
+        except _lib.KGLibraryError as e:
+            raise ValueError(str(e)) from None
+        return LabelSource(inst.labels, n=len(stats), stats=stats)
+
+    @property
+    def shape(self):
+        return tuple(int(v) for v in self.labels.shape)
+
+    def __len__(self):
+        return self.n if self.jobs is None else len(self.jobs)
+
+    def on(self, dev):
+        """the label map as a contiguous device int32 [h, w] on dev (a host map is uploaded once and kept)"""
+        if self._on is None or self._on.device != dev:
+            self._on = self.labels.to(dev).contiguous() if torch.is_tensor(self.labels) else ops.h2d(self.labels, dev)
+        return self._on
+
+    def job_rows(self, img, lab):
+        """The rows (img, id, y1, x1, y2, x2) of this source as image `img` of a batch, in two halves: (host int32 [m, 2] = (img, id),
+        host int32 [m, 4] boxes, None) or, when the boxes are device stats, (the same, None, device int32 [m, 4]); lab = on(dev)."""
+        from . import _labelmaps
+        if self.jobs is not None:
+            return np.concatenate([np.full((len(self.jobs), 1), img, np.int32), self.jobs[:, :1]], 1), self.jobs[:, 1:], None
+        stats = self.stats
+        if self.n and stats is None:
+            from . import labelmetrics
+            stats = labelmetrics.label_stats_device(lab, self.n)[0]          # no copy back: an id without pixels has an empty box there
+        if torch.is_tensor(stats) and self.n:
+            if stats.device != lab.device:
+                raise ValueError("sampleprep.LabelSource: the stats tensor must be on the batch's device")
+            head = np.stack([np.full(self.n, img, np.int32), np.arange(1, self.n + 1, dtype=np.int32)], 1)
+            return head, None, stats[:, 1:5]
+        rows = _labelmaps.jobs_from_stats(stats, img) if self.n else np.zeros((0, 6), np.int32)
+        return rows[:, :2], rows[:, 2:], None
+
+
+def _label_route(masks):
+    """True when every entry is a LabelSource, False when none is; a mixed batch is refused."""
+    k = sum(isinstance(m, LabelSource) for m in masks)
+    if k not in (0, len(masks)):
+        raise ValueError("sampleprep: a batch is either all label sources (LabelSource) or all mask sources, not a mix of the two")
+    return k > 0
+
+
+def _jobs_upload(rows):
+    """rows: LabelSource.job_rows of every image.  -> flat int32: what of the batch's job table travels with the image table.  With all
+    boxes known on the host that is the table itself, [ntot, 6]; when some are device stats it is the (img, id) columns [ntot, 2], then
+    the host boxes [., 4] in image order."""
+    heads = np.concatenate([hd for hd, _, _ in rows]).reshape(-1, 2)
+    if any(d is not None for _, _, d in rows):
+        return np.concatenate([heads.reshape(-1)] + [b.reshape(-1) for _, b, _ in rows if b is not None]).astype(np.int32)
+    return np.concatenate([heads, np.concatenate([b for _, b, _ in rows]).reshape(-1, 4)], 1).astype(np.int32).reshape(-1)
+
+
+def _jobs_device(rows, up, ntot):
+    """up: _jobs_upload(rows) on the device.  -> the batch's job table, device int32 [ntot, 6]: `up` itself, or -- with device stats --
+    its (img, id) columns beside the boxes of every image in order, joined by a device concatenation."""
+    if all(d is None for _, _, d in rows):
+        return up.view(ntot, 6)
+    at, boxes = 2 * ntot, []
+    for _, b, d in rows:
+        boxes.append(d if b is None else up[at:at + b.size].view(-1, 4))
+        at += 0 if b is None else b.size
+    return torch.cat([up[:2 * ntot].view(ntot, 2), torch.cat(boxes)], 1)
+
+
 def prepare_batch_full(images, masks, params, input_h, input_w, device=None):
     """prepare_batch with everything it computed (PreparedBatch)."""
+    from_labels = _label_route(masks)                        # (before the device is touched: a mixed batch is refused anywhere)
     dev = _device(device)
     H, W = int(input_h), int(input_w)
     N = len(images)
@@ -192,23 +317,40 @@ def prepare_batch_full(images, masks, params, input_h, input_w, device=None):
         if len(shp) != 3:
             raise ValueError("sampleprep: images must be uint8 [h, w, 3]")
         resolved.append(params[i].resolved(shp[0], shp[1]))
+        if from_labels and masks[i].shape != tuple(int(v) for v in shp[:2]):
+            raise ValueError(f"sampleprep: a label map of {masks[i].shape} does not have the image's size {tuple(shp[:2])}")
     with torch.cuda.device(dev):
+        rows = []                                            # label sources: LabelSource.job_rows of every image
         for i in range(N):
             img = _image_on(images[i], dev)
             h, w = int(img.shape[0]), int(img.shape[1])
-            mh, mptr, bits, n, ld = _masks_on(masks[i], h, w, dev)
+            if from_labels:
+                mh = masks[i].on(dev)
+                rows.append(masks[i].job_rows(i, mh))
+                mptr, bits, n, ld = mh.data_ptr(), False, len(masks[i]), 0
+            else:
+                mh, mptr, bits, n, ld = _masks_on(masks[i], h, w, dev)
             holders += [img, mh]
             delta, alpha, perm, He, We, oy, ox = resolved[i]
-            flags = (_MIRROR_W if params[i].mirror_w else 0) | (_MIRROR_H if params[i].mirror_h else 0) | (_BITS if bits else 0)
-            rec[i] = (img.data_ptr(), mptr if n else 0, h, w, He, We, oy, ox, flags, perm[0] | perm[1] << 2 | perm[2] << 4,
+            flags = (_MIRROR_W if params[i].mirror_w else 0) | (_MIRROR_H if params[i].mirror_h else 0) | (_BITS if bits else 0) | \
+                (_LABELS if from_labels else 0)
+            rec[i] = (img.data_ptr(), mptr if n or from_labels else 0, h, w, He, We, oy, ox, flags, perm[0] | perm[1] << 2 | perm[2] << 4,
                       np.float32(delta), np.float32(alpha), ntot, n, ld, 0)
             ntot += n
-        # one upload: the image table, then the image of every instance
-        inst_img = np.repeat(np.arange(N, dtype=np.int32), rec["n"])
-        tab = np.concatenate([rec.view(np.uint8), inst_img.view(np.uint8)])
+        if from_labels:
+            # one upload: the image table, then what the host knows of the job table
+            tab = np.concatenate([rec.view(np.uint8), _jobs_upload(rows).view(np.uint8)])
+        else:
+            # one upload: the image table, then the image of every instance
+            inst_img = np.repeat(np.arange(N, dtype=np.int32), rec["n"])
+            tab = np.concatenate([rec.view(np.uint8), inst_img.view(np.uint8)])
         tab_d = ops.h2d(tab, dev)
         rec_p = _lib.c_void_p(tab_d.data_ptr())
         inst_p = _lib.c_void_p(tab_d.data_ptr() + rec.nbytes)
+        if from_labels:
+            jobs_d = _jobs_device(rows, tab_d[rec.nbytes:].view(torch.int32), ntot)
+            holders.append(jobs_d)
+            inst_p = ptr(jobs_d)
         s = stream_ptr()
         img_out = torch.empty(N, 3, H, W, dtype=torch.float32, device=dev)
         _lib.call("kg_sp_image", rec_p, N, H, W, ptr(img_out), s)
@@ -220,7 +362,11 @@ def prepare_batch_full(images, masks, params, input_h, input_w, device=None):
         keep_d = cells[n_host:n_host + ntot]
         kp_d = cells[n_host + ntot:n_host + 41 * ntot].view(torch.float32).view(4, ntot, 5, 2)
         box_d = cells[n_host + 41 * ntot:]
-        _lib.call("kg_sp_warp_masks", rec_p, inst_p, ntot, H, W, ptr(warped) if ntot else None, ptr(box_d) if ntot else None, s)
+        if from_labels:
+            _lib.call("kg_sp_warp_labels", rec_p, N, inst_p if ntot else None, ntot, H, W, ptr(warped) if ntot else None,
+                      ptr(box_d) if ntot else None, s)
+        else:
+            _lib.call("kg_sp_warp_masks", rec_p, inst_p, ntot, H, W, ptr(warped) if ntot else None, ptr(box_d) if ntot else None, s)
         _lib.call("kg_sp_boxes", rec_p, N, ptr(box_d) if ntot else None, ntot, cfg.KP_RADIUS, ptr(counts_d), ptr(gtb_d) if ntot else None,
                   ptr(kp_d) if ntot else None, ptr(keep_d) if ntot else None, s)
         # the batch's only device -> host copy: the counts and the gt_bboxes rows
@@ -251,8 +397,94 @@ def prepare_batch_full(images, masks, params, input_h, input_w, device=None):
 
 def prepare_batch(images, masks, params, input_h, input_w, device=None):
     """images: N uint8 [h,w,3] arrays or tensors (host or device, any sizes); masks: per image the [n,h,w] instance masks as a device
-    uint8 / float32 tensor, a BitMasks or a host NumPy array; params: N SampleParams (draw_train_params / identity_params).
+    uint8 / float32 tensor, a BitMasks or a host NumPy array, or -- for all images of the batch or for none -- a LabelSource; params: N
+    SampleParams (draw_train_params / identity_params).
     Returns collater's tuple (img, gt_c0, gt_c1, gt_c2, gt_c3, instance_masks, bboxes_c0) with device tensors throughout, except the
     [m,5] box arrays of the last element, which SEG_loss matches on the host."""
     b = prepare_batch_full(images, masks, params, input_h, input_w, device)
     return (b.img,) + b.gt + (b.instance_masks, b.gt_bboxes)
+
+
+def warp_labels(labels_list, params, input_h, input_w, device=None):
+    """The label maps themselves through the transform: labels_list = N int32 [h, w] device tensors or host integer arrays (any sizes),
+    params = N SampleParams -> device int32 [N, H, W], out[i][y][x] = labels_i[sy][sx] inside the paste window and 0 outside
+    (kg_sp_warp_labelmap, one launch).  Ground truth at the network's size, for labelmetrics against a prediction made there."""
+    dev = _device(device)
+    H, W = int(input_h), int(input_w)
+    N = len(labels_list)
+    if N == 0 or len(params) != N:
+        raise ValueError("sampleprep: labels_list and params must be non-empty lists of one length")
+    if H <= 0 or W <= 0 or H % 8 or W % 8 or W > MAX_WIDTH:
+        raise ValueError(f"sampleprep: the network input {H} x {W} must be multiples of 8 (KGnet's pyramid), at most {MAX_WIDTH} wide")
+    srcs = [m if isinstance(m, LabelSource) else LabelSource(m, n=0) for m in labels_list]
+    rec = np.zeros(N, _REC)
+    resolved = [p.resolved(*s.shape) for p, s in zip(params, srcs)]
+    with torch.cuda.device(dev):
+        maps = [s.on(dev) for s in srcs]
+        for i, (lab, p) in enumerate(zip(maps, params)):
+            _, _, _, He, We, oy, ox = resolved[i]
+            flags = (_MIRROR_W if p.mirror_w else 0) | (_MIRROR_H if p.mirror_h else 0) | _LABELS
+            rec[i] = (0, lab.data_ptr(), lab.shape[0], lab.shape[1], He, We, oy, ox, flags, 0, np.float32(0), np.float32(1), 0, 0, 0, 0)
+        tab_d = ops.h2d(rec.view(np.uint8), dev)
+        out = torch.empty(N, H, W, dtype=torch.int32, device=dev)
+        _lib.call("kg_sp_warp_labelmap", ptr(tab_d), N, H, W, ptr(out), stream_ptr())
+    return out
+
+
+# ---- host statements of the label route (NumPy; the yardstick of the GPU tests) ---------------------------------------------------------
+
+def source_index_host(size, ce, off, mirror, dsize):
+    """The composed map of one axis (the one tests/sampleprep_ref.py states): destination index -> source index, -1 outside the paste
+    window.  v = min(floor(d * scale), ce - 1) with scale = 1 / (dsize / ce) in double; mirrored, v = ce - 1 - v; s = v - off."""
+    scale = 1.0 / (float(dsize) / float(ce))
+    v = np.minimum(np.floor(np.arange(dsize, dtype=np.float64) * scale).astype(np.int64), ce - 1)
+    if mirror:
+        v = ce - 1 - v
+    s = v - off
+    return np.where((s >= 0) & (s < size), s, -1)
+
+
+def _host_map(fn, labels):
+    lab = labels.cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
+    if lab.ndim != 2 or lab.dtype.kind not in "iu" or lab.size == 0:
+        raise ValueError(f"sampleprep.{fn}: a label map must be a non-empty integer array [h, w]")
+    return lab.astype(np.int64)
+
+
+def _host_axes(lab, p, H, W):
+    h, w = lab.shape
+    _, _, _, He, We, oy, ox = p.resolved(h, w)
+    return source_index_host(h, He, oy, p.mirror_h, H), source_index_host(w, We, ox, p.mirror_w, W)
+
+
+def warp_labels_host(labels_list, params, input_h, input_w):
+    """warp_labels in NumPy -> int32 [N, H, W]: labels[sy][sx] where sy and sx lie inside the paste window, 0 elsewhere."""
+    H, W = int(input_h), int(input_w)
+    out = np.zeros((len(labels_list), H, W), np.int32)
+    for i, (labels, p) in enumerate(zip(labels_list, params)):
+        lab = _host_map("warp_labels_host", labels)
+        sy, sx = _host_axes(lab, p, H, W)
+        inside = (sy >= 0)[:, None] & (sx >= 0)[None, :]
+        out[i] = np.where(inside, lab[np.maximum(sy, 0)][:, np.maximum(sx, 0)], 0)
+    return out
+
+
+def label_masks_host(labels, jobs, params, input_h, input_w):
+    """The masks kg_sp_warp_labels makes for ONE image, in NumPy: labels = integer [h, w]; jobs = integers [m, 5] = (id, y1, x1, y2, x2);
+    params = the image's SampleParams -> uint8 [m, H, W].  Pixel (y, x) of row k is 1 iff its source index (sy, sx) lies inside the paste
+    window, inside the job's half-open box clamped to [0, h] x [0, w], and labels[sy][sx] == id; otherwise 0."""
+    H, W = int(input_h), int(input_w)
+    lab = _host_map("label_masks_host", labels)
+    h, w = lab.shape
+    j = np.asarray(jobs, np.int64).reshape(-1, 5)
+    sy, sx = _host_axes(lab, params, H, W)
+    at = lab[np.maximum(sy, 0)][:, np.maximum(sx, 0)]                                    # [H, W]: the label every output pixel looks at
+    y1, x1 = np.clip(j[:, 1], 0, h), np.clip(j[:, 2], 0, w)
+    y2, x2 = np.clip(j[:, 3], 0, h), np.clip(j[:, 4], 0, w)
+    rows = (sy[None, :] >= 0) & (sy[None, :] >= y1[:, None]) & (sy[None, :] < y2[:, None])   # [m, H]
+    cols = (sx[None, :] >= 0) & (sx[None, :] >= x1[:, None]) & (sx[None, :] < x2[:, None])   # [m, W]
+    out = np.empty((len(j), H, W), np.uint8)
+    for a in range(0, len(j), 1024):
+        b = min(a + 1024, len(j))
+        out[a:b] = rows[a:b, :, None] & cols[a:b, None, :] & (at[None] == j[a:b, 0, None, None])
+    return out
