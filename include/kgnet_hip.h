@@ -979,6 +979,36 @@ int kg_label_border_d2(const int* a, const int* b, int nimg, int H, int W, const
 #define KG_CROPS_MASKED 2
 int kg_label_crops(const int* labels, int nimg, int H, int W, const void* image, int channels, int elem_bytes, const int* jobs, int m, int OH,
                    int OW, int flags, int fill, void* patches, unsigned char* masks, void* stream);
+/* Linking label maps (csrc/linking.hip; linking.py states the semantics in NumPy): which values of ANOTHER map lie under the pixels of an
+ * instance -- the overlap lists behind tracks through time-lapse frames, planes stitched into a volume and child / parent relations.
+ * kg_label_overlaps: a = device int32 [nimg_a][H][W], b = device int32 [nimg_b][H][W], ANY int32 values (compared only); b may be the
+ * same buffer as a (frames of one stack, img_b = img_a + 1); jobs = device int32 [m][11] rows {img_a, id, y1, x1, y2, x2, img_b, dy, dx,
+ * resume, after} (half-open box), written by the caller -> out = device int64 [m][5 + 2 * slots] rows {count, more, area, zero, outside,
+ * (value, pixels) x slots}, 1 <= slots <= 64, every element written; out overlaps neither map nor the job table.
+ * With P = the pixels of the box, clamped to the map, of image img_a of a that hold id, the PARTNER of a pixel (y, x) of P is the pixel
+ * (y + dy, x + dx) of image img_b of b.  area = |P|; outside = the pixels of P whose partner does not lie in the map; zero = those whose
+ * partner holds 0; pixels[v] = those whose partner holds v, for every v != 0.  area = zero + outside + the sum of pixels[v] over all v.
+ * The ids of the two maps are unrelated: id itself is an ordinary partner value, and so are INT_MIN, -1 and INT_MAX.  The rows of bands
+ * that tile a box merge by value (pixels add; area, zero and outside add) to the row of the box.
+ * The row lists the partner values v != 0 with pixels[v] > 0 in ASCENDING SIGNED ORDER, with resume != 0 only those > after (after is
+ * ignored when resume == 0); count = the slots filled (<= slots); more = 1 exactly when a further qualifying value exists beyond the
+ * last one written; unused slots are zeros.  area, zero and outside are over all of P on every row, a resumed one included.  A caller
+ * pages a long list by launching the job again with resume = 1 and after = the last value it got.
+ * A job either of whose image indices lies outside its [0, nimg), whose box is empty or inverted, or whose id the box does not hold gets
+ * a row of zeros and reads nothing else.
+ * SIZE RULE.  H, W <= 32768 as for kg_label_measure: a count stays at or below 2^30 and fits int64; nimg_a * H * W and nimg_b * H * W
+ * <= 2^31 - 1.
+ * INDEX RULE.  No value read from device memory becomes an index: the job table is the one device-read table, its box is clamped to the
+ * map before any address is formed, img_a and img_b are used only inside (unsigned)img < (unsigned)nimg predicates that empty the box,
+ * the partner coordinate is formed in 64 bits and used only inside (unsigned long long)(y + dy) < H and (unsigned long long)(x + dx) < W
+ * before its address exists (dy / dx of INT_MIN / INT_MAX read nothing), and resume / after are compared only; label values of either
+ * map are compared, counted and stored only.  No atomics and no hash table: one workgroup per job extracts the values in order as
+ * kg_label_neighbours does -- at most slots + 1 walks per job, the header counts on the first, and the same row from run to run.
+ * One launch whatever m is; m == 0 is valid and launches nothing (jobs and out may then be NULL).  Validates on the host before any HIP
+ * call (null pointers, nimg_a, nimg_b, H, W > 0, the size rule, slots, m >= 0, 4-byte alignment of a, b and jobs, 8 of out, out apart
+ * from a, b and jobs) and never synchronises. */
+int kg_label_overlaps(const int* a, int nimg_a, const int* b, int nimg_b, int H, int W, const int* jobs, int m, int slots, long long* out,
+                      void* stream);
 
 /* ---- per-box segmentation branch (KGnet.py:246-267, 321-350): ragged row bookkeeping ---- */
 int kg_seg_build_rows(const int* boxtab8, int nb, int* rowdesc, int* row2box, int* srcrow, void* stream);

@@ -1,5 +1,5 @@
 """The argument and batch layer of the label-map modules (instances, tiling, labelmetrics, polygons, components, measure, distance,
-neighbours, runlengths, contours, hulls, intensity, split, texture, thinning, boundaries, crops), one owner per rule.  fn is the public function the message names.
+neighbours, runlengths, contours, hulls, intensity, split, texture, thinning, boundaries, crops, linking), one owner per rule.  fn is the public function the message names.
 
     maps       host_maps, device_maps; with the side bound: MAX_SIDE, side, host_stack, device_stack
     job tables host_jobs, upload_jobs, device_jobs, instance_jobs, batch_jobs; counts, jobs_from_stats, and the n / jobs / stats arguments

@@ -117,6 +117,7 @@ _SIGS = {
     "kg_label_regrow": [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P],
     "kg_label_inscribed": [P, P, c_int, c_int, c_int, P, c_int, P, P],
     "kg_label_neighbours": [P, c_int, c_int, c_int, c_int, P, c_int, c_int, P, P],
+    "kg_label_overlaps": [P, c_int, P, c_int, c_int, c_int, P, c_int, c_int, P, P],
     "kg_label_run_counts": [P, c_int, c_int, c_int, P, c_int, P, P],
     "kg_label_runs": [P, c_int, c_int, c_int, P, c_int, P, c_int, P],
     "kg_runs_paint": [P, c_int, c_int, c_int, c_int, P, P],

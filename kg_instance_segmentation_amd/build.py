@@ -58,6 +58,7 @@ SOURCES = {
     "thinning.hip": [],
     "boundaries.hip": [],
     "crops.hip": [],
+    "linking.hip": [],
 }
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-Wall", "-Wno-unused-function"]

@@ -1,6 +1,6 @@
 // label_common.h -- what the label-map kernels share (instances.hip, tiling.hip, labelmetrics.hip, components.hip, measure.hip,
 // distance.hip, neighbours.hip, runlengths.hip, contours.hip, polygons.hip, hulls.hip, intensity.hip, split.hip, texture.hip,
-// thinning.hip, boundaries.hip, crops.hip; paste.hip for the bit-mask leading dimension; sampleprep.hip for the job box and the host
+// thinning.hip, boundaries.hip, crops.hip, linking.hip; paste.hip for the bit-mask leading dimension; sampleprep.hip for the job box and the host
 // checks of kg_sp_warp_labels): wave reductions, the clamped job box and its walk, the block combine of four wave partials, the
 // row-segment run walk, per-image ranges passed by value, and the host argument checks -- among them the side bound KG_LABEL_MAX_SIDE,
 // the block that opens a per-job entry (kg_check_job_stack), the image check (kg_check_image) and the overlap test (kg_apart).
