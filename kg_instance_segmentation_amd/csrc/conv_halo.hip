@@ -17,12 +17,6 @@
 #include <type_traits>
 #include <utility>
 #include <stdlib.h>
-#ifndef KG_HALO_SETPRIO
-#define KG_HALO_SETPRIO 0
-#endif
-#ifndef KG_NARROW_V2
-#define KG_NARROW_V2 1      // narrow (kp / short) chunks of the grouped second-layer heads: kernel-column stages + sliding halo-row window
-#endif
 
 __device__ uint4 kg_halo_zero_line[8];   // 128 zero bytes: source of the padding pixels of a halo
 
@@ -191,7 +185,6 @@ __global__ __launch_bounds__(WC * WPX * 64) void conv_halo_kernel(const HaloArgs
 
     auto mma = [&](auto mk, const bf16x8 (&af)[4], const bf16x8 (&bfr)[4]) {
         constexpr int MK = decltype(mk)::value;
-        if (KG_HALO_SETPRIO) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int i = 0; i < 4; ++i)
             if ((MK >> i) & 1) {
@@ -199,7 +192,6 @@ __global__ __launch_bounds__(WC * WPX * 64) void conv_halo_kernel(const HaloArgs
                 for (int j = 0; j < 4; ++j)
                     acc[i][j] = KG_MFMA16(af[i], bfr[j], acc[i][j]);
             }
-        if (KG_HALO_SETPRIO) __builtin_amdgcn_s_setprio(0);
     };
 
     int ci_first = (GM == 1 && a.head_split) ? biy * a.grp_chunks : 0;
@@ -287,7 +279,6 @@ __global__ __launch_bounds__(WC * WPX * 64) void conv_halo_kernel(const HaloArgs
             if (head_n < 2) {
                 constexpr int ROWB = 7 * 2048;
                 const int wave_n = __builtin_amdgcn_readfirstlane(wave);
-#if KG_NARROW_V2
                 // Round 4: the stage of the narrow ring is a kernel COLUMN (the 7 taps (ky, kx) of one kx), not a kernel row, and the B side is
                 // walked as a sliding window over halo ROWS: for a fixed (kx, k-step) the four output rows of a wave and the seven ky taps touch
                 // only 10 distinct halo-row fragments -- row R serves every (output row j, tap ky) with j + ky = R.  A step (kx, k-step, ky)
@@ -364,67 +355,6 @@ __global__ __launch_bounds__(WC * WPX * 64) void conv_halo_kernel(const HaloArgs
                         [&]<int... Ns>(std::integer_sequence<int, Ns...>) { (stepn(std::integral_constant<int, Ns>{}), ...); }(std::make_integer_sequence<int, 2 * KS>{});
                     }
                 };
-#else
-                const bf16_t* nsrc[2];
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {                     // piece e of a row: tap kx = e >> 7, row rho = (e >> 3) & 15, 16-byte slot e & 7
-                    const int e = tid + k * 512, kxl = e >> 7, rho = (e >> 3) & 15, sl = e & 7;
-                    const int r = 16 * (rho >> 2) + 4 * head_n + (rho & 3);
-                    const int key = 2 * (rho >> 2) + ((rho >> 1) & 1);
-                    nsrc[k] = a.w + (long)r * a.K + (long)kxl * a.cin_pad + cc * 64 + ((sl ^ key) * 8);
-                }
-                auto nload = [&](int ky) {                        // kernel row ky -> stage ky % 3 (896 pieces: waves 0..5 issue two loads, 6..7 one)
-                    unsigned char* dst = wbuf + (ky % 3) * ROWB + wave_n * 1024;
-                    const long ro = (long)ky * 7 * a.cin_pad;
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(nsrc[0] + ro),
-                                                     (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-                    if (wave_n < 6)
-                        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(nsrc[1] + ro),
-                                                         (__attribute__((address_space(3))) void*)(dst + 8192), 16, 0, 0);
-                };
-                nload(0); nload(1);
-                int a_n[2];
-                {
-                    const int keyl = 2 * (lm >> 2) + ((lm >> 1) & 1);
-#pragma unroll
-                    for (int s2 = 0; s2 < 2; ++s2) a_n[s2] = lm * 128 + (((4 * s2 + g) ^ keyl) * 16);
-                }
-                const unsigned ldsn = lds_addr(smem);
-                auto narrow = [&](auto hc) {
-                    constexpr int HD = decltype(hc)::value;
-#pragma unroll 1
-                    for (int ky = 0; ky < KS; ++ky) {
-                        if (ky + 1 < KS) {                        // row ky has landed; the loads of row ky+1 may stay in flight
-                            if (wave_n < 6) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-                            else asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-                        } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                        __builtin_amdgcn_s_barrier();
-                        asm volatile("" ::: "memory");
-                        if (ky + 2 < KS) nload(ky + 2);           // into the stage of row ky-1, which every wave has left
-                        const unsigned wa = ldsn + HALO_BYTES + (ky % 3) * ROWB;
-                        const unsigned hrow = ldsn + ky * (HWD * 128);
-                        bf16x8 fa[2], fb[2][4];
-                        auto rd = [&](auto nc) {
-                            constexpr int N = decltype(nc)::value, KX = N >> 1, S2 = N & 1, B = N & 1;
-                            lds_rd128<KX * 2048>(fa[B], wa + a_n[S2]);
-                            const unsigned ba = hrow + kb[KX][S2];
-                            lds_rd128<KX * 128>(fb[B][0], ba); lds_rd128<KX * 128 + HWD * 128>(fb[B][1], ba);
-                            lds_rd128<KX * 128 + 2 * HWD * 128>(fb[B][2], ba); lds_rd128<KX * 128 + 3 * HWD * 128>(fb[B][3], ba);
-                        };
-                        auto stepn = [&](auto nc) {
-                            constexpr int N = decltype(nc)::value, B = N & 1;
-                            if constexpr (N + 1 < 2 * KS) { rd(std::integral_constant<int, N + 1>{}); asm volatile("s_waitcnt lgkmcnt(5)" ::: "memory"); }
-                            else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                            asm volatile("" : "+v"(fa[B]), "+v"(fb[B][0]), "+v"(fb[B][1]), "+v"(fb[B][2]), "+v"(fb[B][3]));
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) acc[HD][j] = KG_MFMA16(fa[B], fb[B][j], acc[HD][j]);
-                            __builtin_amdgcn_sched_barrier(0);
-                        };
-                        rd(std::integral_constant<int, 0>{});
-                        [&]<int... Ns>(std::integer_sequence<int, Ns...>) { (stepn(std::integral_constant<int, Ns>{}), ...); }(std::make_integer_sequence<int, 2 * KS>{});
-                    }
-                };
-#endif
                 if (head_n == 0) narrow(std::integral_constant<int, 0>{});
                 else narrow(std::integral_constant<int, 1>{});
                 continue;

@@ -4,14 +4,18 @@ Activations are 2-D bf16 "rows" tensors [rows, C] with unit channel stride; the 
 exceed C when the tensor is a channel slice of a wider (concat) buffer.  PyTorch only owns memory
 and streams here; every arithmetic kernel is hand-written HIP behind the C ABI.
 """
-import functools
 import math
 import os
 
 import torch
 
-from . import _lib
+from . import _lib, routes
 from ._lib import c_int, c_long, c_float, c_double, ptr, stream_ptr
+from .routes import WGRAD_TR, round_up, vplanes      # (vplanes: bench.py reads ops.vplanes)
+# The routing rules are routes.py's: the package reads none of the names below, and assigning to one changes no launch (set routes.USE_WS instead).
+from .routes import CONV_TINY_TILES, CONV_TINY_WGS, USE_WS, halo_wgrad_splits, wgrad_splits  # noqa: F401
+USE_HALO = USE_C3 = USE_1X1 = GATHER_1X1 = IM2COL_WGRAD = True
+HALO_WC = 0
 
 BF16 = torch.bfloat16
 F16 = torch.float16      # rows of the half-precision build (libkgnet_hip_f16.so, csrc/kg_common.h): 11 significant bits per plane
@@ -209,12 +213,6 @@ def pl(a=None, b=None, c=None, y=None, w=1, scale=None, oscale=None):
     return st
 
 
-def vplanes(xP, wP):
-    """number of virtual channel planes of a packed weight = kept products x_i * w_j, i + j < max(xP, wP) (csrc/kg_common.h kg_plane_pairs)"""
-    T = max(xP, wP)
-    return sum(1 for i in range(xP) for j in range(wP) if i + j < T)
-
-
 def _rows(t):
     t = base(t)
     assert t.dim() == 2 and t.dtype in (BF16, F16) and (t.shape[1] == 1 or t.stride(1) == 1), (t.shape, t.stride(), t.dtype)
@@ -223,10 +221,6 @@ def _rows(t):
 
 def ld(t):
     return base(t).stride(0)
-
-
-def round_up(a, b):
-    return (a + b - 1) // b * b
 
 
 class PackQueue:
@@ -424,21 +418,10 @@ def conv7_narrow(x, pw, cout, N, H, W, y, mask=None, chan_lo=0, chan_slot=8, fli
               ld(mb) if mb is not None else 0, pw.K, 1 if flip else 0, stream_ptr(), fmt=fmt_of(xb))
 
 
-USE_HALO = True
-WGRAD128 = True           # (module constants: tests and probes may flip them; the environment switches of rounds 1-5 are gone, docs/history.md)
-USE_C3 = True
-IM2COL_WGRAD = True
-
-
-HALO_WC = 0               # tuning override of the halo kernels' cout blocks per workgroup (0 = library default)
-
-
-USE_WS = True             # the weight-stationary 64 -> 64 kernel (conv3_ws.hip)
-
-
-def conv_halo(x, pw, cout, N, H, W, KS, y=None, y_f32=None, bias=None, res=None, mask=None, relu=False, flip=False, wc=0,
+def conv_halo(x, pw, cout, N, H, W, KS, y=None, y_f32=None, bias=None, res=None, mask=None, relu=False, flip=False,
               tiletab=None, total_rows=0, k1skip=False, algo_cin=None, tiletab16=None, oscale=None, tiletab8=None, narrow=0):
-    """Stride-1 "same" KSxKS conv (or its input gradient when flip) with the input halo resident in LDS.
+    """Stride-1 "same" KSxKS conv (or its input gradient when flip) with the input halo resident in LDS; routes.halo_entry picks the
+    weight-stationary (conv3_ws.hip), the 64-channel (conv3_c64.hip) or the general kernel (conv_halo.hip).
     tiletab (int32 [ntiles,4] device tensor): ragged boxes instead of N images of HxW.
     k1skip (7x7 only): the packed weights are zero for channels 32..63 of every 64-channel chunk.
     narrow = 8 / 16 (7x7 input gradient of a conv whose dY rows carry data in channels 0..7 / 8..23 only; pw from PackedWeight.pack_narrow): 4 / 2 kernel
@@ -446,29 +429,26 @@ def conv_halo(x, pw, cout, N, H, W, KS, y=None, y_f32=None, bias=None, res=None,
     algo_cin: number of input channels that carry data (FLOP accounting of bench.py's timer; unused here)."""
     flush_packs()
     assert nplanes(x)[0] == pw.xP, (nplanes(x), pw.xP)
-    if (USE_WS and KS == 3 and pw.cin_pad == 64 and cout == 64 and pw.xP == 2 and pw.wP == 2 and y is not None and y_f32 is None and res is None
-            and mask is None and not flip and oscale is None and wc == 0 and HALO_WC == 0 and (tiletab is None or tiletab8 is not None)
-            and nplanes(y)[0] <= 2 and not conv_stats_armed()):
-        # full-resolution 64 -> 64 convs on hi + lo planes: weights in registers, two workgroups per CU (conv3_ws.hip)
+    rows_out = y is not None and y_f32 is None
+    entry = routes.halo_entry(KS, pw.cin_pad, cout, pw.xP, pw.wP, nplanes(y)[0], nplanes(res)[0], rows_out, res is not None, mask is not None, flip,
+                              oscale is not None, _STATS_ARMED[0], tiletab is not None, tiletab8 is not None, tiletab16 is not None)
+    if entry == "kg_conv3x3_ws":
         _lib.call("kg_conv3x3_ws", ptr(_rows(x)), ptr(pw.buf), ptr(bias), ptr(base(y)), N, H, W, ld(x), ld(y), pw.K, 1 if relu else 0,
                   ptr(tiletab8), tiletab8.shape[0] if tiletab8 is not None else 0, pl(a=x, y=y, w=pw.wP), stream_ptr(), fmt=fmt_of(x))
         return
     planes = pl(a=x, b=res, y=y, w=pw.wP, oscale=oscale)      # (oscale: folded inference BatchNorm, y = act(acc * oscale + bias + res))
     x, y, res, mask = base(x), base(y), base(res), base(mask)
-    if (USE_C3 and planes is None and KS == 3 and pw.cin_pad == 64 and y is not None and y_f32 is None and wc == 0 and HALO_WC == 0
-            and (tiletab is None or tiletab16 is not None)):
-        # 64 input channels: persistent kernel with resident weights and double-buffered halos (conv3_c64.hip)
-        flush_packs()
+    if entry == "kg_conv3x3_c64":
         _lib.call("kg_conv3x3_c64", ptr(_rows(x)), ptr(pw.buf), ptr(bias), ptr(y), ptr(res), ptr(mask), N, H, W, ld(x), cout, ld(y),
                   ld(res) if res is not None else 0, ld(mask) if mask is not None else 0, pw.K, 1 if flip else 0, 1 if relu else 0,
                   ptr(tiletab16), tiletab16.shape[0] if tiletab16 is not None else 0, stream_ptr(), fmt=fmt_of(x))
         return
-    wc = wc or HALO_WC
+    wc = 0
     if k1skip:
-        assert KS == 7 and wc in (0, 1)
+        assert KS == 7
         wc = 1 | 256
     if narrow:
-        assert KS == 7 and wc in (0, 1) and flip and narrow in (8, 16) and planes is None and tiletab is None and y is not None and y_f32 is None
+        assert KS == 7 and flip and narrow in (8, 16) and planes is None and tiletab is None and rows_out
         wc = 1 | (512 if narrow == 8 else 1024)
     f32_C = 0
     if y_f32 is not None:
@@ -477,10 +457,6 @@ def conv_halo(x, pw, cout, N, H, W, KS, y=None, y_f32=None, bias=None, res=None,
               pw.cin_pad, ld(x), cout, ld(y) if y is not None else 0, ld(res) if res is not None else 0,
               ld(mask) if mask is not None else 0, pw.K, KS, 1 if flip else 0, 1 if relu else 0, f32_C, wc, ptr(tiletab),
               tiletab.shape[0] if tiletab is not None else 0, total_rows, planes, stream_ptr(), fmt=fmt_of(x))
-
-
-USE_1X1 = True
-GATHER_1X1 = True
 
 
 def conv1x1(x, pw, cout, y, bias=None, res=None, mask=None, relu=False):
@@ -494,124 +470,57 @@ def conv1x1(x, pw, cout, y, bias=None, res=None, mask=None, relu=False):
 
 
 def can_1x1(x, pw, KH, stride, pad, y, y_f32, res=None):
-    if pw.vp > 1 or any(nplanes(t)[0] > 1 for t in (x, y, res)):
-        return False      # split-bf16 planes: the gather kernel (conv_gather.hip) walks the virtual channels
-    if GATHER_1X1 and pw.cin_pad >= 192 and pw.rows > 64:
-        return False      # compute-heavy 1x1 (K >= 192, Cout > 64): the LDS-ring gather kernel (conv_gather.hip) is faster
-    return (USE_1X1 and KH == 1 and stride == 1 and pad == 0 and y is not None and y_f32 is None and pw.cin_pad % 64 == 0
-            and 64 <= pw.cin_pad <= 1024 and x.shape[1] >= pw.cin_pad and y.shape[0] == x.shape[0])
-
-
-CONV_TINY_WGS = 96        # regular workgroups below which a launch goes to the split-K kernel (0 = never)
-CONV_TINY_TILES = 384
+    return routes.can_1x1(KH, stride, pad, pw.cin_pad, x.shape[1], pw.rows, pw.vp > 1 or any(nplanes(t)[0] > 1 for t in (x, y, res)),
+                          y is not None and y_f32 is None, y is not None and y.shape[0] == x.shape[0])
 
 
 def conv_auto(x, pw, cout, geom, N, y=None, y_f32=None, bias=None, res=None, mask=None, relu=False, transposed=False, tile=0, oscale=None,
               tiny=True):
-    """Dense conv forward (transposed=False) or input gradient (True): picks the LDS-halo kernel for stride-1
+    """Dense conv forward (transposed=False) or input gradient (True) on the kernel routes.dense_kind picks: the LDS-halo kernels for stride-1
     "same" 3x3/7x7 convs over 64-channel-aligned inputs, else the gather implicit GEMM.  tiny: launches whose output gives the
     regular kernels fewer than CONV_TINY_WGS workgroups (single-image inference, the deepest layers of a small batch) may go to
-    the split-K kernel (conv_tiny.hip); False for a conv that is armed for BatchNorm statistics (that epilogue lives in the regular kernels)."""
+    the split-K kernel (conv_tiny.hip); False for a conv that is armed for BatchNorm statistics (that epilogue lives in the regular kernels).  Square kernels only (asserted): the planner is asked with one kernel size."""
     M, H, W, OH, OW, KH, KW, stride, pad = geom
-    halo_ok = (USE_HALO and stride == 1 and KH == KW and KH in (3, 7) and pad == KH // 2 and pw.cin_pad % 64 == 0
-               and x.shape[1] >= pw.cin_pad and not (y_f32 is not None and (res is not None or mask is not None)))
-    if tiny and tile == 0 and CONV_TINY_WGS and y is not None and y_f32 is None and pw.cin_pad % 64 == 0 and x.shape[1] >= pw.cin_pad and KH * KW <= 9:
-        wgs = (N * math.ceil(OH / 16) * math.ceil(OW / 32) * math.ceil(cout / 64)) if halo_ok else math.ceil(M / 256) * math.ceil(cout / 128)
-        tiles = math.ceil(M / 64) * math.ceil(cout / 64)
-        # (no operand reuse inside a 64 x 64 tile: measured 1.75 ns per (tile, K unit) against 0.85 us per K unit of a regular workgroup
-        # -- past ~400 tiles the regular kernel's single round is as fast)
-        if wgs < CONV_TINY_WGS and wgs < tiles <= CONV_TINY_TILES:
-            conv_igemm(x, pw, cout, geom, y=y, bias=bias, res=res, mask=mask, relu=relu, mode=1 if transposed else 0, tile=6, oscale=oscale)
-            return "tiny"
-    if (USE_HALO and stride == 1 and KH == KW and KH in (3, 7) and pad == KH // 2 and pw.cin_pad % 64 == 0
-            and x.shape[1] >= pw.cin_pad and not (y_f32 is not None and (res is not None or mask is not None))):
+    assert KH == KW, geom
+    planed = pw.vp > 1 or nplanes(x)[0] > 1 or nplanes(y)[0] > 1 or nplanes(res)[0] > 1
+    kind = routes.dense_kind(M, N, OH, OW, KH, stride, pad, pw.cin_pad, x.shape[1], pw.rows, planed, cout, y is not None and y_f32 is None,
+                             res is not None, mask is not None, oscale is not None, KH == 1 and y is not None and y.shape[0] == x.shape[0], tile, tiny)
+    if kind == "tiny":
+        conv_igemm(x, pw, cout, geom, y=y, bias=bias, res=res, mask=mask, relu=relu, mode=1 if transposed else 0, tile=6, oscale=oscale)
+    elif kind == "halo":
         conv_halo(x, pw, cout, N, OH, OW, KH, y=y, y_f32=y_f32, bias=bias, res=res, mask=mask, relu=relu, flip=transposed, oscale=oscale)
-        return "halo"
-    if KH == KW and oscale is None and can_1x1(x, pw, KH, stride, pad, y, y_f32, res):
+    elif kind == "1x1":
         conv1x1(x, pw, cout, y, bias=bias, res=res, mask=mask, relu=relu)
-        return "1x1"
-    conv_igemm(x, pw, cout, geom, y=y, y_f32=y_f32, bias=bias, res=res, mask=mask, relu=relu, mode=1 if transposed else 0, tile=tile, oscale=oscale)
-    return "igemm"
-
-
-WGRAD_RING = True
-WGRAD_RING_WGS = 256      # workgroups of a ring launch (one 96 / 144 KB workgroup per CU)
-
-
-WGRAD_TR = [True]      # mirror of the library's kg_set_wgrad_tr switch (set_wgrad_tr below keeps the two in step)
+    else:
+        conv_igemm(x, pw, cout, geom, y=y, y_f32=y_f32, bias=bias, res=res, mask=mask, relu=relu, mode=1 if transposed else 0, tile=tile, oscale=oscale)
+    return kind
 
 
 def set_wgrad_tr(on):
-    """test switch of kg_conv2d_wgrad: LDS transpose reads (default) or scalar fragment loads -- both libraries and the split sizing"""
+    """test switch of kg_conv2d_wgrad: LDS transpose reads (default) or scalar fragment loads -- both libraries and the split sizing (routes.WGRAD_TR)"""
     WGRAD_TR[0] = bool(on)
     for fmt in (0, 1):
         _lib.call("kg_set_wgrad_tr", 1 if on else 0, fmt=fmt)
 
 
-def wgrad_splits(M, cin_lim, cout_lim, taps, nelem):
-    """pixel splits of kg_conv2d_wgrad, sized for the tile the library will pick: the conditions below are kg_conv2d_wgrad's own
-    (conv_wgrad.hip: ring iff transpose reads && cin >= 128 && cout >= 64; 128 x 128 iff transpose reads
-    && cin, cout >= 128)"""
-    chunks = math.ceil(M / 64)
-    if WGRAD_RING and WGRAD_TR[0] and cin_lim >= 128 and cout_lim >= 64:
-        # conv_wgrad_ring_kernel (256 x 128 tiles, or 128 x 128 below 256 couts; 144 / 96 KB of LDS: one workgroup per CU): one round of at
-        # most 256 workgroups
-        base = math.ceil(cin_lim / 128) * math.ceil(cout_lim / (256 if cout_lim >= 256 else 128)) * taps
-        s = max(1, min(WGRAD_RING_WGS // base if base <= WGRAD_RING_WGS else 1, max(1, chunks // 3)))
-        while s > 1 and s * nelem * 4 > (768 << 20):
-            s -= 1
-        return s
-    t = 128 if (WGRAD128 and WGRAD_TR[0] and cin_lim >= 128 and cout_lim >= 128) else 64      # output tile of kg_conv2d_wgrad
-    base = math.ceil(cin_lim / t) * math.ceil(cout_lim / t) * taps
-    s = max(1, min(math.ceil(2048 / base), max(1, chunks // 4)))
-    while s > 1 and s * nelem * 4 > (768 << 20):
-        s -= 1
-    return s
-
-
-@functools.lru_cache(maxsize=4096)      # (the search walks up to 2048 candidates; ~110 calls per step with a few dozen distinct shapes)
-def halo_wgrad_splits(nblk, tiles, cit, taps, nelem, cus=256):
-    """Pixel splits of kg_conv2d_wgrad_halo: one workgroup per CU is resident (2 x 47..78 KB of LDS + ~250 VGPRs x 8 waves), so
-    the launch runs in ceil(nblk * S / 256) rounds; pick S by a small cost model (round count x tiles per workgroup + per-workgroup
-    prologue / partial write + the reduction's bytes) instead of a fixed 2 rounds -- 192 x 2 = 384 workgroups is 1.5 rounds."""
-    tile_us = 256 * 64 * cit * taps * 2 / 5.3e6          # one 16x16 tile at ~1.35 PFLOP/s / 256 CUs
-    best, best_t = 1, None
-    for S in range(1, max(1, min(tiles, 2048 // nblk if nblk <= 2048 else 1)) + 1):
-        if S > 1 and S * nelem * 4 > (768 << 20):
-            break
-        rounds = math.ceil(nblk * S / cus)
-        t = rounds * (math.ceil(tiles / S) * tile_us + 10.0) + S * nelem * 8 / 3e6
-        if S >= 8 and S % 8 == 0:
-            t *= 0.97                                    # multiples of 8 enable the kernel's XCD-aware block mapping
-        if best_t is None or t < best_t:
-            best, best_t = S, t
-    return best
-
-
-def wgrad_pairs(x, dy):
-    """(x plane, dY plane) products of a weight gradient over split-bf16 operands: i + j < max(xP, dP)."""
-    xP, dP = nplanes(x)[0], nplanes(dy)[0]
-    T = max(xP, dP)
-    return sorted(((i, j) for j in range(dP) for i in range(xP) if i + j < T), key=lambda p: -(p[0] + p[1]))      # smallest products first
-
-
 def conv_wgrad(x, dy, cin, cout, geom, grads, mode=0, rowdesc=None, accumulate=False, N=None, tiletab16=None, bias_out=None):
     """grads: list of (fp32 OIHW grad tensor, cout_offset, cout_count) sharing x (fused heads) or one entry.
-    Dense stride-1 "same" 3x3/7x7 convs (N given) use the LDS-halo kernel, everything else the gather kernel.
+    Dense stride-1 "same" 3x3/7x7 convs (N given) use the LDS-halo kernel, everything else the gather kernel (routes.wgrad).
     bias_out (fp32 [cout], optional): receives the bias gradient (sum of dy over rows) -- for free inside the halo kernel
     (one more all-ones unit on a wave with an idle unit slot), with kg_bias_grad otherwise.
-    x / dy may be split-bf16 (PT): every kept plane product is one more set of pixel-split partials for the fixed-order reduction."""
+    x / dy may be split-bf16 (PT): every kept plane product is one more set of pixel-split partials for the fixed-order reduction.  Square kernels only (asserted): the planner is asked with one kernel size."""
     M, H, W, OH, OW, KH, KW, stride, pad = geom
-    pairs = wgrad_pairs(x, dy)
-    xps, dps = nplanes(x)[1], nplanes(dy)[1]
-    planed = len(pairs) > 1 or nplanes(x)[0] > 1 or nplanes(dy)[0] > 1
+    assert KH == KW, geom
+    xP, xps = nplanes(x)
     xb, dyb = _rows(x), _rows(dy)
-    if IM2COL_WGRAD and mode == 0 and N is not None and cin <= 4 and KH * KW >= 25 and len(grads) == 1 and not accumulate:
+    kind, cin_lim, cout_lim, _, _, S, fused_bias = routes.wgrad(M, N, H, W, KH, stride, pad, cin, cout, xb.shape[1], dyb.shape[1], xP, nplanes(dy)[0], mode,
+                                                                len(grads) == 1, accumulate, tiletab16.shape[0] if tiletab16 is not None else None,
+                                                                bias_out is not None)
+    if kind == "im2col":
         # stem conv1 (3 -> 64, 7x7 s2): im2col to [M][taps*cin] and ONE 1x1 weight-gradient GEMM instead of 49 per-tap launches
         # that pad 3 channels to a 64-wide tile (planes: im2col is a gather, so every plane is gathered separately)
         Kc = KH * KW * cin
         Kpad = round_up(Kc, 8)
-        xP = nplanes(x)[0]
         col = alloc_pt(M, Kpad, xP, xb.device, zero=Kpad != Kc, dtype=xb.dtype)
         for p_ in range(xP):
             _lib.call("kg_im2col_small", ctypes_offset(xb, p_ * xps), ctypes_offset(col.t, p_ * col.ps), N, H, W, OH, OW, KH, KW, stride, pad, cin,
@@ -623,37 +532,23 @@ def conv_wgrad(x, dy, cin, cout, geom, grads, mode=0, rowdesc=None, accumulate=F
         g.copy_(tmp.view(cnt, KH * KW, cin).permute(0, 2, 1).reshape(g.shape))     # [co][tap][ci] -> OIHW
         if bias_out is not None:
             bias_grad(dy, cout, bias_out)
-        return "im2col"
-    cin_lim = min(round_up(cin, 8), xb.shape[1])
-    cout_lim = min(round_up(cout, 8), dyb.shape[1])
+        return kind
     nelem = cout * KH * KW * cin
-    halo = (USE_HALO and stride == 1 and KH == KW and KH in (3, 7) and pad == KH // 2
-            and ((mode == 0 and N is not None) or (mode == 2 and tiletab16 is not None)))
-    np_ = len(pairs)
     planes = pl(a=x, b=dy)
-    if halo:
-        cit = (32 if (cout_lim <= 16 and cin_lim >= 32 and bias_out is not None and not planed) else 16) if KH == 7 else 64   # input channels per workgroup (wgrad_halo.hip)
-        nblk = math.ceil(cin_lim / cit) * math.ceil(cout_lim / 64)
-        tiles = tiletab16.shape[0] if tiletab16 is not None else N * math.ceil(H / 16) * math.ceil(W / 16)
-        S = halo_wgrad_splits(nblk, tiles * np_, cit, KH * KW, nelem)      # (plane products = more tiles to walk)
-        fused_bias = bias_out is not None and not planed
+    dbp = None
+    if kind == "halo":
         part, big = WGQ.alloc(S * nelem, xb.device, "wgrad", extra=S * cout if fused_bias else 0)
-        dbp = None
         if fused_bias:
             dbp, big2 = WGQ.alloc(S * cout, xb.device, "wgrad_bias")
             big = big or big2
         _lib.call("kg_conv2d_wgrad_halo", ptr(xb), ptr(dyb), ptr(part), N or 0, H, W, ld(xb), ld(dyb), cin, cout, cin_lim, cout_lim, KH, S,
                   c_long(nelem), ptr(tiletab16), tiletab16.shape[0] if tiletab16 is not None else 0, ptr(dbp), planes, stream_ptr(), fmt=fmt_of(x))
-        if dbp is None and bias_out is not None:       # planed operands: the all-ones unit would count every plane product
-            bias_grad(dy, cout, bias_out, accumulate=accumulate)
     else:
-        dbp = None
-        S = wgrad_splits(M * np_, cin_lim, cout_lim, KH * KW, nelem)
         part, big = WGQ.alloc(S * nelem, xb.device, "wgrad")
         _lib.call("kg_conv2d_wgrad", ptr(xb), ptr(dyb), ptr(part), ptr(rowdesc), M, H, W, OH, OW, ld(xb), ld(dyb), cin, cout, cin_lim, cout_lim,
                   KH, KW, stride, pad, 1, mode, S, c_long(nelem), planes, stream_ptr(), fmt=fmt_of(xb))
-        if bias_out is not None:
-            bias_grad(dy, cout, bias_out, accumulate=accumulate)
+    if dbp is None and bias_out is not None:       # (gather kernel, or planed operands: the all-ones unit would count every plane product)
+        bias_grad(dy, cout, bias_out, accumulate=accumulate)
     contiguous = all(grads[i][1] + grads[i][2] == grads[i + 1][1] for i in range(len(grads) - 1))
     import ctypes
     acc = 1 if accumulate else 0
@@ -669,12 +564,7 @@ def conv_wgrad(x, dy, cin, cout, geom, grads, mode=0, rowdesc=None, accumulate=F
             _lib.call("kg_wgrad_reduce", ctypes_offset(part, off * KH * KW * cin), ptr(g), cnt, cin, KH, KW, S, c_long(nelem), acc, stream_ptr())
     if big:
         WGQ.flush()
-    return "halo" if halo else "gather"
-
-
-def wgrad_halo(x, dy, part, N, H, W, cin, cout, cin_lim, cout_lim, KS, S, nelem, tiletab16=None, dbp=None):
-    _lib.call("kg_conv2d_wgrad_halo", ptr(x), ptr(dy), ptr(part), N, H, W, ld(x), ld(dy), cin, cout, cin_lim, cout_lim, KS, S,
-              c_long(nelem), ptr(tiletab16), tiletab16.shape[0] if tiletab16 is not None else 0, ptr(dbp), None, stream_ptr(), fmt=fmt_of(x))
+    return kind
 
 
 def ctypes_offset(t, elem_off):

@@ -12,7 +12,7 @@ import os
 import numpy as np
 import torch
 
-from . import arch, ops, _lib
+from . import arch, ops, routes, _lib
 from ._lib import ptr, stream_ptr, c_long
 from .ops import BF16, PT, PackedWeight
 
@@ -355,13 +355,6 @@ class SegBranch:
         _lib.call("kg_rows_gather_f32", ptr(frows), frows.stride(0), sr, ptr(ops.base(dst)), ops.ld(dst), c_long(nrows), C,
                   ops.pl(y=dst), stream_ptr(), fmt=ops.fmt_of(dst))
 
-    @staticmethod
-    def _head(t, M):
-        """first M rows of a rows tensor (torch tensor or ops.PT)"""
-        if t is None:
-            return None
-        return t.rows(0, M) if isinstance(t, PT) else t[:M]
-
     def alloc(self, rows, C, dev):
         return ops.alloc_pt(rows, C, self.P_, dev, dtype=self.dt)
 
@@ -372,16 +365,17 @@ class SegBranch:
         """Ragged conv (mode 2) or its input gradient (mode 3).  3x3 convs over 64-channel-aligned inputs run on the
         LDS-halo kernel with one (box, 16x32 tile) entry per workgroup; the rest on the gather implicit GEMM.
         `tiles` = (tile table of the first `M` rows' boxes); boxes are a prefix, so a prefix of the table is used."""
-        if (ops.USE_HALO and k == 3 and tiles is not None and tiles.shape[0] > 0 and pw.cin_pad % 64 == 0 and x.shape[1] >= pw.cin_pad
-                and M >= 0.35 * tiles.shape[0] * 512):     # tiles mostly full: tiny deep-level crops stay on the gather kernel
+        route = routes.ragged_conv(k, M, tiles.shape[0] if tiles is not None else 0, pw.cin_pad, x.shape[1], pw.rows,
+                                   pw.vp > 1 or ops.nplanes(x)[0] > 1 or ops.nplanes(y)[0] > 1, y is not None and y_f32 is None,
+                                   y is not None and min(M, x.shape[0]) == min(M, y.shape[0]))
+        if route == "halo":
             ops.conv_halo(x, pw, cout, 0, 0, 0, 3, y=y, y_f32=y_f32, bias=bias, relu=relu, mask=mask, flip=(mode == 3),
                           tiletab=tiles, total_rows=M, tiletab16=tiles16, tiletab8=tiles8)
-            return
-        if k == 1 and y is not None and ops.can_1x1(self._head(x, M), pw, 1, 1, 0, self._head(y, M), y_f32):
+        elif route == "1x1":
             ops.conv1x1(ops.base(x)[:M], pw, cout, ops.base(y)[:M], bias=bias, mask=mask[:M] if mask is not None else None, relu=relu)
-            return
-        geom = (M, 0, 0, M, 1, k, k, 1, (k - 1) // 2)
-        ops.conv_igemm(x, pw, cout, geom, y=y, y_f32=y_f32, bias=bias, relu=relu, mask=mask, mode=mode, rowdesc=rowdesc)
+        else:
+            geom = (M, 0, 0, M, 1, k, k, 1, (k - 1) // 2)
+            ops.conv_igemm(x, pw, cout, geom, y=y, y_f32=y_f32, bias=bias, relu=relu, mask=mask, mode=mode, rowdesc=rowdesc)
 
     @staticmethod
     def T8(plan, l, nboxes):
@@ -463,7 +457,7 @@ class SegBranch:
         geom = (M, 0, 0, M, 1, k, k, 1, (k - 1) // 2)
         eng = self.m._engine
         gw = eng.new_grad(key + ".weight", w)
-        use16 = t16 if (k == 3 and t16 is not None and M >= 0.35 * t16.shape[0] * 256) else None
+        use16 = t16 if routes.ragged_wgrad_halo(k, M, t16.shape[0] if t16 is not None else None) else None
         db = eng.new_grad(key + ".bias", self.P(key + ".bias"))
         pw_ = min(self.Pg, self.m._engine.pw)
         gw_ = g

@@ -1,13 +1,13 @@
 """Launch classes of the DENSE convolutions and one small parity case per class (TEST INFRASTRUCTURE, not product; imports no GPU library).
 
-Everything Engine launches through ops.conv_auto / ops.conv_wgrad / ops.conv1x1 / ops.conv_halo_heads2 / ops.conv7_narrow is dispatched twice: by
-ops.py (halo / split-K / 1x1 / gather / weight-stationary kernels ...) and again inside the library (launch_halo, kg_launch_conv_gather,
+Everything Engine launches through ops.conv_auto / ops.conv_wgrad / ops.conv1x1 / ops.conv_halo_heads2 / ops.conv7_narrow is dispatched twice: on the
+host by kg_instance_segmentation_amd/routes.py (halo / split-K / 1x1 / gather / weight-stationary kernels ...) and again inside the library (launch_halo, kg_launch_conv_gather,
 kg_launch_conv_tiny, kg_conv1x1, kg_conv2d_wgrad, kg_conv2d_wgrad_halo, kg_launch_conv_small, kg_conv2d_halo_heads2), where fill thresholds
 decide about kernel variants and about a channel / K split that kg_last_kernel does not show.  This module
   * defines the LAUNCH CLASS KEY (`Key`),
-  * restates both levels of dispatch as host arithmetic (`key_*`: from the primitive arguments of an entry point; `plan`: from a case;
-    `key_of_call`: from the arguments of an observed _lib.call) -- thresholds that ops.py exposes are read from ops, the library's own are restated
-    next to the source line they come from, environment switches are read from os.environ as the library reads them,
+  * asks routes.py for the host's decision and restates the library's as host arithmetic (`key_*`: from the primitive arguments of an entry
+    point; `plan`: from a case; `key_of_call`: from the arguments of an observed _lib.call) -- the library's thresholds are restated next to the
+    source line they come from, environment switches are read from os.environ as the library reads them,
   * lists the parity cases (`CASES`), each with the kernel and split state it is MEANT to hit -- tests/test_dense_routes_cpu.py asserts that the plan
     says so, tests/test_gpu_dense_routes.py that the library does so,
   * parses a profiles/*_bench_launches.txt census into keys (`parse_census`) and names the ragged classes that belong to the seg-branch tests
@@ -23,6 +23,8 @@ import re
 
 import torch
 import torch.nn.functional as F
+
+from kg_instance_segmentation_amd import routes
 
 from . import segcases
 
@@ -59,11 +61,6 @@ def cdiv(a, b):
 
 def round_up(a, b):
     return cdiv(a, b) * b
-
-
-def _ops():
-    from kg_instance_segmentation_amd import ops
-    return ops
 
 
 def _env_int(name, default):
@@ -151,7 +148,7 @@ def launch_gather(M, cout, cin_pad, xP, wP, taps):
     n64 = _env_int("KG_GATHER_N64", 512)
     if n64 > 0 and cout <= 64 and cdiv(M, 128) >= n64:         # :297
         return f"conv_gather_kernel<{_b(p2)}, 1>", False
-    nstage = taps * (cin_pad // 32) if p2 else taps * (cin_pad * segcases.vplanes(xP, wP) // 64)
+    nstage = taps * (cin_pad // 32) if p2 else taps * (cin_pad * routes.vplanes(xP, wP) // 64)
     return f"conv_gather_kernel<{_b(p2)}, 2>", gather_split(M, cout, nstage) > 1
 
 
@@ -172,11 +169,9 @@ def conv1x1_kernel(K, cout):
 
 
 def wgrad_kernel(cin_lim, cout_lim, mode, direct):
-    """kg_conv2d_wgrad (csrc/conv_wgrad.hip:517-555) with the LDS transpose reads on (ops.WGRAD_TR)"""
+    """kg_conv2d_wgrad (csrc/conv_wgrad.hip) with the LDS transpose reads on (routes.WGRAD_TR)"""
     if cin_lim >= 128 and cout_lim >= 64:
         return f"conv_wgrad_ring_kernel<{2 if mode >= 2 else (0 if direct else 1)}, {2 if cout_lim >= 256 else 1}>"
-    if cin_lim >= 128 and cout_lim >= 128:      # (never true after the ring test: conv_wgrad128_kernel is unreachable while the ring is on, see UNREACHABLE)
-        return "conv_wgrad128_kernel"
     return "conv_wgrad_kernel"
 
 
@@ -206,7 +201,7 @@ def key_halo(ks, N, H, W, cin_pad, xP, wP, yP, cout, flip, rows_out, bias, res, 
     """kg_conv2d_halo, dense, wc = 1 (csrc/conv_halo.hip:1165-1221).  armed: None / "fwd" / "bwd" (kg_conv_stats_begin / kg_conv_bstats_begin)."""
     want = (flip and ks == 3 and cout % 64 == 0) if armed == "bwd" else (not res and not mask and not relu and not flip)      # :1196
     stat = armed if (armed and rows_out and want) else None
-    vp = segcases.vplanes(xP, wP)
+    vp = routes.vplanes(xP, wP)
     kern, split = launch_halo(ks, N * cdiv(H, 16) * cdiv(W, 32), cout, cin_pad, vp, bool(flip), rows_out, oscale, stat)
     return Key("kg_conv2d_halo", kern, ks, 1, 1 if flip else 0, xP, wP, yP if rows_out else 0, vp, fmt, split,
                _epi(bias=bias, res=res, mask=mask, relu=relu, f32=not rows_out, oscale=oscale, stats=stat == "fwd", bstats=stat == "bwd"))
@@ -214,7 +209,7 @@ def key_halo(ks, N, H, W, cin_pad, xP, wP, yP, cout, flip, rows_out, bias, res, 
 
 def key_igemm(M, cin_pad, xP, wP, yP, cout, k, stride, mode, tile, rows_out, K, bias, res, mask, relu, oscale, armed, fmt):
     """kg_conv2d_igemm, dense modes (csrc/conv_igemm.hip:266-293)"""
-    vp = segcases.vplanes(xP, wP)
+    vp = routes.vplanes(xP, wP)
     taps, stat, split = k * k, None, False
     if tile == 6:
         kern, split = "conv_tiny_kernel", tiny_split(M, cout, vp * cin_pad, taps) > 1
@@ -245,16 +240,16 @@ def key_ws(yP, bias, relu, fmt):
 
 def key_wgrad(H, W, OH, OW, cin_lim, cout_lim, k, stride, pad, mode, S, xP, dP, fmt):
     direct = mode == 0 and k == 1 and stride == 1 and pad == 0 and OH == H and OW == W
-    return Key("kg_conv2d_wgrad", wgrad_kernel(cin_lim, cout_lim, mode, direct), k, stride, mode, xP, dP, 0, segcases.vplanes(xP, dP), fmt, S > 1, frozenset())
+    return Key("kg_conv2d_wgrad", wgrad_kernel(cin_lim, cout_lim, mode, direct), k, stride, mode, xP, dP, 0, routes.vplanes(xP, dP), fmt, S > 1, frozenset())
 
 
 def key_wgrad_halo(ks, cin_lim, cout_lim, dbp, S, xP, dP, fmt):
-    return Key("kg_conv2d_wgrad_halo", wgrad_halo_kernel(ks, cin_lim, cout_lim, dbp), ks, 1, 0, xP, dP, 0, segcases.vplanes(xP, dP), fmt, S > 1,
+    return Key("kg_conv2d_wgrad_halo", wgrad_halo_kernel(ks, cin_lim, cout_lim, dbp), ks, 1, 0, xP, dP, 0, routes.vplanes(xP, dP), fmt, S > 1,
                _epi(dbias=dbp))
 
 
 def key_heads2(N, H, W, C, xP, wP, fmt):
-    vp = segcases.vplanes(xP, wP)
+    vp = routes.vplanes(xP, wP)
     return Key("kg_conv2d_halo_heads2", "conv_halo_kernel<7, 1, 8, 1>", 7, 1, 0, xP, wP, 0, vp, fmt, heads2_split(N, H, W, C, vp), _epi(bias=True, f32=True))
 
 
@@ -262,34 +257,24 @@ def key_narrow(slot, flip, mask, fmt):
     return Key("kg_conv7_narrow", f"conv7_narrow_kernel<{slot}>", 7, 1, 1 if flip else 0, 1, 1, 1, 1, fmt, False, _epi(mask=mask))
 
 
-# ---- ops.py, restated -----------------------------------------------------------------------------------------------------------------
+# ---- the Python level: routes decides, the key_* functions above add what the library does with the launch --------------------------------
 
 def plan_conv_auto(M, N, OH, OW, k, stride, pad, cin_pad, rows_w, K, xP, wP, yP, rP, cout, transposed, rows_out, bias, res, mask, relu, oscale, tile,
                    tiny, armed, fmt):
-    """ops.conv_auto + ops.conv_halo + ops.can_1x1 for an input of at least cin_pad columns: (python-level kind, Key)"""
-    ops = _ops()
-    f32 = not rows_out
+    """ops.conv_auto for an input of at least cin_pad columns and an output of as many rows: (python-level kind, Key)"""
     ep = dict(bias=bias, res=res, mask=mask, relu=relu, oscale=oscale, armed=armed, fmt=fmt)
     mode = 1 if transposed else 0
-    halo_ok = ops.USE_HALO and stride == 1 and k in (3, 7) and pad == k // 2 and cin_pad % 64 == 0 and not (f32 and (res or mask))
-    if tiny and tile == 0 and ops.CONV_TINY_WGS and rows_out and cin_pad % 64 == 0 and k * k <= 9:
-        wgs = N * cdiv(OH, 16) * cdiv(OW, 32) * cdiv(cout, 64) if halo_ok else cdiv(M, 256) * cdiv(cout, 128)
-        tiles = cdiv(M, 64) * cdiv(cout, 64)
-        if wgs < ops.CONV_TINY_WGS and wgs < tiles <= ops.CONV_TINY_TILES:
-            return "tiny", key_igemm(M, cin_pad, xP, wP, yP, cout, k, stride, mode, 6, True, K, **ep)
-    if halo_ok:
-        if (ops.USE_WS and k == 3 and cin_pad == 64 and cout == 64 and xP == 2 and wP == 2 and rows_out and not res and not mask and not transposed
-                and not oscale and ops.HALO_WC == 0 and yP <= 2 and not armed):
-            return "halo", key_ws(yP, bias, relu, fmt)
-        if ops.USE_C3 and xP == wP == yP == rP == 1 and not oscale and k == 3 and cin_pad == 64 and rows_out and ops.HALO_WC == 0:
-            return "halo", key_c64(transposed, bias, res, mask, relu, fmt)
-        return "halo", key_halo(k, N, OH, OW, cin_pad, xP, wP, yP, cout, transposed, rows_out, **ep)
-    planed = segcases.vplanes(xP, wP) > 1 or xP > 1 or yP > 1 or rP > 1
-    heavy = ops.GATHER_1X1 and cin_pad >= 192 and rows_w > 64
-    if (not oscale and not planed and not heavy and ops.USE_1X1 and k == 1 and stride == 1 and pad == 0 and rows_out and cin_pad % 64 == 0
-            and 64 <= cin_pad <= 1024):
-        return "1x1", key_1x1(cin_pad, cout, bias, res, mask, relu, fmt)
-    return "igemm", key_igemm(M, cin_pad, xP, wP, yP, cout, k, stride, mode, tile, rows_out, K, **ep)
+    kind, entry = routes.dense_conv(M, N, OH, OW, k, stride, pad, cin_pad, cin_pad, rows_w, xP, wP, yP, rP, cout, transposed, rows_out, res, mask,
+                                    oscale, True, tile, tiny, armed)
+    if entry == "kg_conv3x3_ws":
+        return kind, key_ws(yP, bias, relu, fmt)
+    if entry == "kg_conv3x3_c64":
+        return kind, key_c64(transposed, bias, res, mask, relu, fmt)
+    if entry == "kg_conv2d_halo":
+        return kind, key_halo(k, N, OH, OW, cin_pad, xP, wP, yP, cout, transposed, rows_out, **ep)
+    if entry == "kg_conv1x1":
+        return kind, key_1x1(cin_pad, cout, bias, res, mask, relu, fmt)
+    return kind, key_igemm(M, cin_pad, xP, wP, yP, cout, k, stride, mode, 6 if kind == "tiny" else tile, rows_out, K, **ep)
 
 
 def packed_K(taps, cin_pad, vp):
@@ -298,23 +283,15 @@ def packed_K(taps, cin_pad, vp):
 
 
 def plan_conv_wgrad(M, N, H, W, OH, OW, k, stride, pad, cin, cout, xcols, dcols, xP, dP, bias_out, fmt):
-    """ops.conv_wgrad (mode 0, one gradient tensor, N given): (python-level kind, Key, pixel splits S)"""
-    ops = _ops()
-    np_ = segcases.vplanes(xP, dP)
-    planed = np_ > 1 or xP > 1 or dP > 1
-    if ops.IM2COL_WGRAD and cin <= 4 and k * k >= 25:
+    """ops.conv_wgrad (mode 0, one gradient tensor): (python-level kind, Key, pixel splits S)"""
+    kind, cin_lim, cout_lim, _, _, S, dbp = routes.wgrad(M, N, H, W, k, stride, pad, cin, cout, xcols, dcols, xP, dP, 0, True, False, None, bool(bias_out))
+    if kind == "im2col":      # (ops.conv_wgrad calls itself on the im2col matrix: a 1x1 weight gradient over OH x OW "images", no N, no bias)
         Kc = k * k * cin
         _, key, S = plan_conv_wgrad(M, None, OH, OW, OH, OW, 1, 1, 0, Kc, cout, round_up(Kc, 8), dcols, xP, dP, False, fmt)
-        return "im2col", key, S
-    cin_lim, cout_lim = min(round_up(cin, 8), xcols), min(round_up(cout, 8), dcols)
-    nelem = cout * k * k * cin
-    if ops.USE_HALO and stride == 1 and k in (3, 7) and pad == k // 2 and N is not None:
-        cit = (32 if (cout_lim <= 16 and cin_lim >= 32 and bias_out and not planed) else 16) if k == 7 else 64
-        nblk = cdiv(cin_lim, cit) * cdiv(cout_lim, 64)
-        S = ops.halo_wgrad_splits(nblk, N * cdiv(H, 16) * cdiv(W, 16) * np_, cit, k * k, nelem)
-        return "halo", key_wgrad_halo(k, cin_lim, cout_lim, bool(bias_out and not planed), S, xP, dP, fmt), S
-    S = ops.wgrad_splits(M * np_, cin_lim, cout_lim, k * k, nelem)
-    return "gather", key_wgrad(H, W, OH, OW, cin_lim, cout_lim, k, stride, pad, 0, S, xP, dP, fmt), S
+        return kind, key, S
+    if kind == "halo":
+        return kind, key_wgrad_halo(k, cin_lim, cout_lim, dbp, S, xP, dP, fmt), S
+    return kind, key_wgrad(H, W, OH, OW, cin_lim, cout_lim, k, stride, pad, 0, S, xP, dP, fmt), S
 
 
 # ---- the cases ------------------------------------------------------------------------------------------------------------------------
@@ -340,7 +317,7 @@ def plan(c):
     """(python-level kind, Key, extra) the case will produce, under the case's environment"""
     with environment(c.env):
         P = c.P
-        vp = segcases.vplanes(P, P)
+        vp = routes.vplanes(P, P)
         if c.op == "fwd":
             cin_pad = round_up(c.cin, 8)
             kind, key = plan_conv_auto(c.N * c.OH * c.OW, c.N, c.OH, c.OW, c.k, c.stride, c.pad, cin_pad, c.cout, packed_K(c.k * c.k, cin_pad, vp), P, P, P,
@@ -804,8 +781,6 @@ KERNEL_NAMES = (
 )
 # names a launcher can note that NO dense launch through ops.py reaches, with the reason (found while writing the planner)
 UNREACHABLE = {
-    "conv_wgrad128_kernel": "kg_conv2d_wgrad tests ring (cin_lim >= 128 && cout_lim >= 64) before 128 x 128 (cin_lim, cout_lim >= 128): with the LDS "
-                            "transpose reads on, every launch that qualifies for the 128 x 128 kernel takes the ring kernel; without them neither runs",
     "conv_small_kernel": "ops.PackedWeight pads K of an 8-channel weight to whole tap quads, which is exactly kg_launch_conv_small's condition for the MFMA variant",
     "conv_wgrad_ring_kernel<2, 1>": "mode 2 (ragged rows): seg branch, SEG_FAMILY",
     "conv_wgrad_ring_kernel<2, 2>": "mode 2 (ragged rows): seg branch, SEG_FAMILY",
@@ -940,7 +915,7 @@ def parse_census(text):
             split = None
             if fam == "conv_gather_kernel":
                 xP = iv["xP"]
-                split = launch_gather(iv["M"], iv["cout"], iv["cinp"], xP, xP if prod == segcases.vplanes(xP, xP) else 1, k * k)[1]
+                split = launch_gather(iv["M"], iv["cout"], iv["cinp"], xP, xP if prod == routes.vplanes(xP, xP) else 1, k * k)[1]
             key = Key(entry, kern, k, iv.get("stride", 1), mode, iv.get("xP"), None, iv.get("yP"), prod, None, split, None)
         else:        # weight gradients: route=im2col lines name the 1x1 GEMM the stem's gradient becomes (k = 1 on the kernel's side)
             im2col = kv.get("route") == "im2col"

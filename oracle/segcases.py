@@ -3,9 +3,9 @@
 SegBranch (kg_instance_segmentation_amd/seg.py) chooses the kernel of every ragged convolution from the DATA: how well the boxes of a launch fill
 their tiles, how many workgroups the launch has, how many pyramid levels accept a box.  This module
   * defines named, seeded box populations on a c0 map of 256 x 512 (levels 256 x 512 ... 16 x 32) that between them reach every route,
-  * restates the routing rules of SegBranch.rconv / SegBranch.conv_bwd / ops.conv_halo / launch_halo (csrc/conv_halo.hip) as plain host
-    arithmetic over seg.crop_rects (`plan_routes`) -- tests/test_seg_routes_cpu.py asserts the coverage table from it and
-    tests/test_gpu_seg_routes.py asserts that the launches observed on the GPU are exactly the planned ones,
+  * walks the launches of SegBranch.run_forward / _run_backward over seg.crop_rects, asks routes.py (the planner SegBranch.rconv / conv_bwd /
+    ops.conv_halo ask) for the route of each and restates launch_halo's channel split (csrc/conv_halo.hip) as host arithmetic (`plan_routes`)
+    -- tests/test_seg_routes_cpu.py asserts the coverage table from it and tests/test_gpu_seg_routes.py asserts that the launches observed on the GPU are exactly the planned ones,
   * builds the seeded feature maps, the float64 / float32 oracle runs and the per-region metrics of the gradient tests.
 Route tags are "<entry point>[/<what distinguishes the route>]"; the same tags are produced from the arguments of the observed calls
 (`tag_of_call`)."""
@@ -16,6 +16,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from kg_instance_segmentation_amd import routes
+
 from . import net as onet
 
 H0, W0 = 256, 512
@@ -25,7 +27,6 @@ SKIP = [(64, 64, 128), (256, 64, 128), (512, 256, 512), (1024, 512, 1024)]     #
 FEAT_RMS = [0.045, 0.11, 0.16, 0.16, 0.28]                                # per-level rms of the calibrated fixture (tests/golden/net_cal.*.npz, a/b.eval.feat*)
 # planes of (seg branch forward, seg branch backward) per policy (engine.PRECISIONS, columns 4 and 5)
 POLICY_PLANES = {"fp32": (2, 1), "fp32b2": (2, 2), "half": (1, 1), "bf16": (1, 1)}
-HALO_FILL = 0.35                                                          # SegBranch.rconv / conv_bwd: rows >= HALO_FILL * tiles * tile pixels
 HALO_SPLIT_WGS = 128                                                      # launch_halo: chunk split of launches with at most this many workgroups
 
 
@@ -120,11 +121,6 @@ def features(boxes, seed, scale=1.0):
 
 # ---- the plan: what SegBranch.make_plan / run_forward / _run_backward will launch ----------------------------------------------------
 
-def vplanes(xP, wP):
-    T = max(xP, wP)
-    return sum(1 for i in range(xP) for j in range(wP) if i + j < T)
-
-
 def halo_ksplit(tiles, cout, cin_pad, vp):
     """launch_halo (csrc/conv_halo.hip): number of channel-chunk parts Z of a ragged 3x3 kg_conv2d_halo launch (1 = not split)"""
     wgs = tiles * ((cout + 63) // 64)
@@ -190,16 +186,18 @@ def plan_routes(boxes, policy, crop_rects=None):
         return p, out
 
     def conv3(pas, l, conv, nbox, cin_pad, cout, xP, wP, yP, flip, t8):
-        """SegBranch.rconv (k = 3) + ops.conv_halo"""
+        """SegBranch.rconv (k = 3: rows output, bias / ReLU forward, mask in the flipped launches, tables of 16 x 32 and 16 x 16 tiles, of 8-pixel
+        tiles where t8) + ops.conv_halo"""
         M, t32 = _rows(p, l, nbox), _tiles(p, l, nbox, 16, 32)
         info = {"M": M, "tiles32": t32, "fill32": M / (t32 * 512.0)}
-        if cin_pad % 64 == 0 and M >= HALO_FILL * t32 * 512:
-            if cin_pad == 64 and cout == 64 and xP == 2 and wP == 2 and not flip and t8 and yP <= 2:
+        if routes.ragged_conv(3, M, t32, cin_pad, cin_pad, cout, xP > 1 or wP > 1 or yP > 1, True, True) == "halo":
+            entry = routes.halo_entry(3, cin_pad, cout, xP, wP, yP, 1, True, False, flip, flip, False, False, True, t8, True)
+            if entry == "kg_conv3x3_ws":
                 tag = "kg_conv3x3_ws/tiles8"
-            elif xP == 1 and wP == 1 and yP == 1 and cin_pad == 64:
+            elif entry == "kg_conv3x3_c64":
                 tag = "kg_conv3x3_c64/tiles16" + ("+flip" if flip else "")
             else:
-                Z = halo_ksplit(t32, cout, cin_pad, vplanes(xP, wP))
+                Z = halo_ksplit(t32, cout, cin_pad, routes.vplanes(xP, wP))
                 info.update(wgs=t32 * ((cout + 63) // 64), ksplit=Z)
                 tag = "kg_conv2d_halo/tiles32" + ("+flip" if flip else "") + ("+split" if Z > 1 else "")
         else:
@@ -208,9 +206,7 @@ def plan_routes(boxes, policy, crop_rects=None):
 
     def conv1(pas, l, conv, M, cin_pad, rows_w, xP, wP, yP, flip):
         """SegBranch.rconv (k = 1) + ops.can_1x1"""
-        planed = vplanes(xP, wP) > 1 or xP > 1 or yP > 1
-        heavy = cin_pad >= 192 and rows_w > 64
-        ok = not planed and not heavy and cin_pad % 64 == 0 and 64 <= cin_pad <= 1024
+        ok = routes.ragged_conv(1, M, 0, cin_pad, cin_pad, rows_w, xP > 1 or wP > 1 or yP > 1, True, True) == "1x1"
         out.append((pas, l, conv, "kg_conv1x1" if ok else f"kg_conv2d_igemm/mode{3 if flip else 2} 1x1", {"M": M}))
 
     def wgrad(l, conv, nbox, k):
@@ -219,7 +215,7 @@ def plan_routes(boxes, policy, crop_rects=None):
         if k == 3:
             t16 = _tiles(p, l, nbox, 16, 16)
             info = {"M": M, "tiles16": t16, "fill16": M / (t16 * 256.0)}
-            tag = "kg_conv2d_wgrad_halo/tiles16" if M >= HALO_FILL * t16 * 256 else "kg_conv2d_wgrad/mode2 3x3"
+            tag = "kg_conv2d_wgrad_halo/tiles16" if routes.ragged_wgrad_halo(3, M, t16) else "kg_conv2d_wgrad/mode2 3x3"
         else:
             info, tag = {"M": M}, "kg_conv2d_wgrad/mode2 1x1"
         out.append(("bwd", l, conv, tag, info))
@@ -275,7 +271,7 @@ KERNEL_FAMILY = {"kg_conv3x3_ws": ("conv3_ws_kernel",), "kg_conv3x3_c64": ("conv
                  "kg_conv1x1": ("conv1x1_kernel", "conv1x1_stream_kernel"),
                  "kg_conv2d_igemm": ("conv_igemm_kernel", "conv_gather_kernel", "conv_small_kernel", "conv_small_mfma_kernel", "conv_tiny_kernel"),
                  "kg_conv2d_wgrad_halo": ("conv_wgrad_halo_kernel", "wgrad_halo_kernel"),
-                 "kg_conv2d_wgrad": ("conv_wgrad_kernel", "conv_wgrad128_kernel", "conv_wgrad_ring_kernel")}
+                 "kg_conv2d_wgrad": ("conv_wgrad_kernel", "conv_wgrad_ring_kernel")}
 TRACKED = set(KERNEL_FAMILY) | {"kg_rows_gather_f32", "kg_rows_gather", "kg_rows_gather_planes", "kg_bilinear_fwd", "kg_bilinear_bwd",
                                 "kg_crop_grad_reduce", "kg_seg_conv3_c1", "kg_seg_build_rows_levels"}
 
@@ -298,7 +294,7 @@ def tag_of_call(name, args):
             return name + "/dense"
         pl = args[25]
         aP, wP = (pl.contents.a_planes, pl.contents.w_planes) if pl is not None else (1, 1)
-        Z = halo_ksplit(args[23], args[12], args[10], vplanes(aP, wP)) if (args[17] == 3 and not _null(args[3]) and _null(args[4])) else 1
+        Z = halo_ksplit(args[23], args[12], args[10], routes.vplanes(aP, wP)) if (args[17] == 3 and not _null(args[3]) and _null(args[4])) else 1
         return name + "/tiles32" + ("+flip" if args[18] else "") + ("+split" if Z > 1 else "")
     if name == "kg_conv2d_igemm":
         return name + f"/mode{args[25]} {args[20]}x{args[21]}" + ("" if not _null(args[7]) else " dense")

@@ -1,6 +1,6 @@
 """Which kernel does every DENSE convolution launch take, and does a small parity case stand behind every class?  (no GPU needed)
 
-oracle/densecases.py restates the dispatch of ops.conv_auto / conv_halo / can_1x1 / conv_wgrad and of the library's launchers (launch_halo,
+oracle/densecases.py asks the host planner (routes.py) what ops.conv_auto / conv_halo / conv_wgrad will call, restates the library's launchers (launch_halo,
 kg_launch_conv_gather, kg_launch_conv_tiny, kg_conv1x1, kg_conv2d_wgrad, kg_conv2d_wgrad_halo, kg_launch_conv_small, kg_conv2d_halo_heads2) as host
 arithmetic and lists one parity case per launch class.  tests/test_gpu_dense_routes.py runs the cases and asserts that the library launches what the
 plan says.  Here the TABLE is asserted:

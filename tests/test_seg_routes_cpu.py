@@ -1,7 +1,7 @@
 """Which kernel does every ragged launch of the seg branch take, per box population?  (no GPU needed)
 
 SegBranch routes its ragged convolutions by the DATA (tile fill, workgroup count, depth of every box).  oracle/segcases.py defines box
-populations and restates the routing rules as host arithmetic (`plan_routes`); here the COVERAGE TABLE is asserted: every route of
+populations and plans the route of every launch from the host planner's answers (routes.py) and launch_halo's restated split (`plan_routes`); here the COVERAGE TABLE is asserted: every route of
 SegBranch.rconv / conv_bwd / ops.conv_halo / launch_halo is planned by at least one population, so that tests/test_gpu_seg_routes.py -- which
 asserts that the launches observed on the GPU equal the planned ones, and compares every box with the float64 oracle -- exercises all of them.
 A change of a threshold, of a population or of the routing that makes a route unreachable fails HERE, naming the route.

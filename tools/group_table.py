@@ -9,7 +9,7 @@ GROUPS = [
     ("7x7 heads: weight gradients wgrad_halo<7,...>", lambda n: "wgrad_halo_kernel<7" in n),
     ("3x3: conv_halo<3> + conv_halo3_w4 + conv3_ws + conv3_c64 + wgrad_halo<3>", lambda n: "conv_halo_kernel<3" in n or "conv_halo3_w4" in n or "conv3_c64" in n or "conv3_ws" in n or "wgrad_halo_kernel<3" in n),
     ("conv_gather", lambda n: "conv_gather" in n),
-    ("gather weight gradients conv_wgrad128 / conv_wgrad", lambda n: "conv_wgrad" in n),
+    ("gather weight gradients conv_wgrad_ring / conv_wgrad", lambda n: "conv_wgrad" in n),
     ("conv1x1_*, conv_small, im2col, conv_igemm", lambda n: "conv1x1" in n or "conv_small" in n or "im2col" in n or "conv_igemm" in n),
     ("BatchNorm (colreduce, bn_*)", lambda n: "colreduce" in n or n.startswith("bn_")),
     ("split reductions + bias gradients", lambda n: "wgrad_reduce" in n or "bias_grad" in n),
